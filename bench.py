@@ -9,7 +9,7 @@ reference restores (osqp_set_default_settings, osqp.py:100-101): rho adapted eve
 test.  `value` is measured in THAT mode (two kernels per step: shared factor until an instance's rho changes,
 per-instance factor behind it); the fixed-rho fork of the same workload is printed beside it as `fixed_rho`.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch (theta already resident in HBM): canonicalise ->
@@ -17,6 +17,9 @@ update -> ADMM solve -> retrieve, for every instance of the rank's shard.  Weak 
 solves its own 100 000 instances; no data-path collective (instances are independent); rank 0
 prints ONE JSON line with the whole-job throughput, the roofline object for the solve kernel and
 the CPU baseline (the scalar-C oracle restatement, timed on the host cores of this box).
+
+The inputs are drawn from fixed seeds, so the same arguments give the same inputs in every run; `--dump-outputs DIR`
+writes what the last timed step computed (`dump_outputs`), so that two builds can be compared output for output.
 """
 
 import argparse
@@ -155,6 +158,27 @@ def make_theta(desc, B: int, seed: int) -> np.ndarray:
     return -2.0 + 4.0 * rng.random((B, p.size))
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6      # a dump's files together, .npy headers included
+
+
+def dump_outputs(res, out_dir: str, seed: int = 0) -> dict:
+    """--dump-outputs: writes what the timed path hands its caller after the last step (BatchResult of DeviceBatch.download:
+    primal / dual solutions in variable / constraint order, objective, residuals, iteration count, status) as <out_dir>/<name>.npy,
+    float64.  A batch above DUMP_LIMIT_BYTES is represented by a fixed, seeded sample of its instances -- the same rows in every
+    file, their indices in instance.npy -- so that two builds run with the same arguments can be compared file for file."""
+    arrays = {'prim': res.prim_flat, 'dual': res.dual_flat, 'obj_val': res.obj_val, 'pri_res': res.pri_res,
+              'dua_res': res.dua_res, 'iter': res.iter, 'status': res.status}
+    B = len(res.iter)
+    row_bytes = 8 * (1 + sum(int(np.prod(a.shape[1:])) for a in arrays.values()))      # (+1: the instance index)
+    n = min(B, (DUMP_LIMIT_BYTES - 4096) // row_bytes)                              # (4096: room for the headers)
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(seed).choice(B, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'instance.npy'), idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), np.ascontiguousarray(a[idx], dtype=np.float64))
+    return {'dir': out_dir, 'instances': int(n), 'of': B, 'files': ['instance'] + list(arrays)}
+
+
 def effective_cpus():
     """CPUs this process may really use: the scheduler affinity mask and the cgroup CPU quota (a lease on a 256-thread host
     is often worth a dozen cores: omp_get_max_threads() says 256, the quota decides).  Returns (count, how it was found)."""
@@ -287,7 +311,11 @@ def main():
     ap.add_argument('--debug-stage', type=int, default=0, help='experiments: the per-instance factor kernel stops after stage k of its set-up (results are garbage)')
     ap.add_argument('--rccl-timeout', type=float, default=60.0, help='seconds ncclCommInitRank may take before the gather falls back to the host transport')
     ap.add_argument('--rccl-lib', default='librccl.so', help='RCCL library of the result gather (CPU tier: the recording stand-in of tests/sim/fake_rccl)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the results of the last timed step (rank 0; a seeded sample of at most 64 MB) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # started as plain `python bench.py --gpus N`: become the launcher -- one rank per GPU through the same
@@ -448,6 +476,7 @@ def main():
     hybrid = desc.solver == 'OSQP' and bool(getattr(solver, '_hybrid', False)) and solver.h is solver.h_shared
     phase = solver.last_phase_ms() if hybrid else None      # split of the last step: (ms shared, ms per-instance, handed over)
     res = dev.download()
+    dumped = dump_outputs(res, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     iters = res.iter
     solved = int((res.status == 1).sum())
     stats = {'mean_iter': float(iters.mean()), 'max_iter': int(iters.max()), 'solved': solved,
@@ -738,6 +767,8 @@ def main():
                 'n': nchk, 'iter_mismatch': int((o['iter'] != res.iter[:nchk]).sum()),
                 'prim_relerr': float(np.abs(po - res.prim_flat[:nchk]).max() / np.abs(po).max()),
                 'dual_relerr': float(np.abs(do - res.dual_flat[:nchk]).max() / np.abs(do).max())}
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         print(json.dumps(out), flush=True)
     dev.free()
     if gather is not None:

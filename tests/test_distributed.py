@@ -196,17 +196,17 @@ def test_host_gather_ignores_the_segment_of_a_killed_run():
     assert not os.path.exists(f'/dev/shm/{name}.ready') and not os.path.exists(f'/dev/shm/{name}')
 
 
-def test_bench_single_rank_json_line_carries_the_contract(sim_lib):
+def test_bench_single_rank_json_line_carries_the_contract(sim_lib, tmp_path):
     """`python bench.py` at N = 1 (emulator library, tiny batch): ONE JSON line with every field of the driver's contract,
-    the `roofline` and `cpu_baseline` objects of the tier, both kernels of the default-mode step under `phases`, and the
-    fixed-rho fork beside the headline value"""
+    the `roofline` and `cpu_baseline` objects of the tier, both kernels of the default-mode step under `phases`, the
+    fixed-rho fork beside the headline value, and (--dump-outputs) the last step's results as float64 .npy files"""
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
     B, steps = 6, 2
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', str(steps), '--warmup', '1', '--workload', 'mpc6',
-                        '--batch', str(B), '--lib', sim_lib, '--generic', '--cpu-seconds', '1'],
+                        '--batch', str(B), '--lib', sim_lib, '--generic', '--cpu-seconds', '1', '--dump-outputs', str(tmp_path / 'out')],
                        capture_output=True, text=True, env=env, timeout=1200)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -233,3 +233,32 @@ def test_bench_single_rank_json_line_carries_the_contract(sim_lib):
     assert set(out['phases']) == {'shared_factor', 'per_instance_factor'}            # default mode: two kernels per step
     assert out['phases']['shared_factor']['instances'] == B
     assert out['fixed_rho']['value'] > 0
+    # the dump: every instance of a batch this small, in the order of the batch, agreeing with the line's statistics
+    dump = {f: np.load(tmp_path / 'out' / f'{f}.npy') for f in out['dump_outputs']['files']}
+    assert out['dump_outputs']['instances'] == out['dump_outputs']['of'] == B
+    assert set(dump) == {'instance', 'prim', 'dual', 'obj_val', 'pri_res', 'dua_res', 'iter', 'status'}
+    assert all(a.dtype == np.float64 and a.shape[0] == B for a in dump.values())
+    assert dump['instance'].tolist() == list(range(B)) and dump['prim'].shape[1] > 0 and dump['dual'].shape[1] > 0
+    assert (dump['status'] == 1).sum() == out['config']['solved'] and dump['iter'].mean() == out['config']['mean_iter']
+    assert np.isfinite(dump['prim']).all() and np.isfinite(dump['obj_val']).all()
+
+
+def test_bench_dump_outputs_samples_a_large_batch(tmp_path, monkeypatch):
+    """a batch above bench.DUMP_LIMIT_BYTES is dumped as a fixed sample of its instances: the same rows in every file and in
+    every run, within the limit"""
+    import bench
+    from cvxpygen_amd.runtime import BatchResult
+    B, n_prim, n_dual = 1000, 5, 3
+    rng = np.random.default_rng(0)
+    res = BatchResult(prim={}, dual={}, obj_val=rng.random(B), iter=np.arange(B, dtype=np.int32), status=np.ones(B, dtype=np.int32),
+                      pri_res=rng.random(B), dua_res=rng.random(B), prim_flat=rng.random((B, n_prim)), dual_flat=rng.random((B, n_dual)))
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 4096 + 100 * 8 * (n_prim + n_dual + 6))
+    a, b = bench.dump_outputs(res, str(tmp_path / 'a')), bench.dump_outputs(res, str(tmp_path / 'b'))
+    assert a['instances'] == 100 and a['of'] == B and a['files'] == b['files']
+    load = {run: {f: np.load(tmp_path / run / f'{f}.npy') for f in a['files']} for run in ('a', 'b')}
+    assert all(np.array_equal(load['a'][f], load['b'][f]) for f in a['files'])
+    assert sum(os.path.getsize(tmp_path / 'a' / f'{f}.npy') for f in a['files']) <= bench.DUMP_LIMIT_BYTES
+    idx = load['a']['instance'].astype(np.int64)
+    assert len(set(idx.tolist())) == 100 and (np.diff(idx) > 0).all()
+    assert np.array_equal(load['a']['iter'], idx) and np.array_equal(load['a']['prim'], res.prim_flat[idx])
+    assert np.array_equal(load['a']['dual'], res.dual_flat[idx]) and np.array_equal(load['a']['obj_val'], res.obj_val[idx])
