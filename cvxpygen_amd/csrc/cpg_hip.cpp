@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "cpg_osqp_kernel.h"
@@ -37,6 +38,15 @@ static void set_error(const std::string &s) { g_err = s; }
 struct DevBuf {   // one device allocation
     void *p = nullptr;
     size_t bytes = 0;
+};
+// the seven result arrays of a batch of B instances on the device (staging of the host-pointer entry points)
+struct ResultBufs {
+    DevBuf prim, dual, obj, pri, dua, iter, status;
+    int ensure(size_t B, const cpg::DevFamily &F);
+    void free();
+    // into the caller's arrays from instance `first` on, queued on `stream`
+    int copy_out(rt_stream_t stream, size_t first, size_t B, const cpg::DevFamily &F, double *prim_h, double *dual_h,
+                 double *obj_h, double *pri_h, double *dua_h, int32_t *iter_h, int32_t *status_h) const;
 };
 
 struct cpg_solver_s {
@@ -74,7 +84,8 @@ struct cpg_solver_s {
     double time_limit = 1e10; int verbose = 1, direct_kkt_solver = 1, presolve_enable = 1;   // accepted, unused
     DevBuf scratch;                     // delta_x / delta_y stash, [waves][G][n + m]
     // staging for the host-pointer entry point
-    DevBuf s_theta, s_prim, s_dual, s_obj, s_pri, s_dua, s_iter, s_status, s_state_in, s_state_out;
+    DevBuf s_theta, s_state_in, s_state_out;
+    ResultBufs s_out;
     struct cpg_pipe_s *pipe = nullptr;  // cpg_hip_solve_batches_pipelined
     std::vector<int> rows_hdr[3];       // host copies of the chunk tables of A_rows / P_rows / At_rows (literal checks of generated kernels)
     // OSQP library defaults the generated shim has no setter for (cpg_hip_set_build_option); restored, like the
@@ -116,6 +127,39 @@ static int rt_sync(cpg_handle_t h) {
 }
 static int rt_set_device(int dev) {
     RT_CHECK(hipSetDevice(dev));
+    return CPG_OK;
+}
+
+static int ensure(DevBuf &b, size_t bytes) {
+    if (b.bytes >= bytes && b.p) return CPG_OK;
+    if (b.p) rt_free(b.p);
+    b.p = nullptr; b.bytes = 0;
+    int rc = rt_malloc(&b.p, bytes);
+    if (rc) return rc;
+    b.bytes = bytes;
+    return CPG_OK;
+}
+static void free_buf(DevBuf &b) { if (b.p) rt_free(b.p); b.p = nullptr; b.bytes = 0; }
+
+int ResultBufs::ensure(size_t B, const cpg::DevFamily &F) {
+    int rc;
+    if ((rc = ::ensure(prim, B * F.n_prim * sizeof(double))) || (rc = ::ensure(dual, B * F.n_dual * sizeof(double))) ||
+        (rc = ::ensure(obj, B * sizeof(double))) || (rc = ::ensure(pri, B * sizeof(double))) || (rc = ::ensure(dua, B * sizeof(double))) ||
+        (rc = ::ensure(iter, B * sizeof(int32_t))) || (rc = ::ensure(status, B * sizeof(int32_t)))) return rc;
+    return CPG_OK;
+}
+void ResultBufs::free() {
+    for (DevBuf *b : {&prim, &dual, &obj, &pri, &dua, &iter, &status}) free_buf(*b);
+}
+int ResultBufs::copy_out(rt_stream_t stream, size_t first, size_t B, const cpg::DevFamily &F, double *prim_h, double *dual_h,
+                         double *obj_h, double *pri_h, double *dua_h, int32_t *iter_h, int32_t *status_h) const {
+    const size_t np = F.n_prim, nd = F.n_dual;
+    const struct { void *dst; const DevBuf &src; size_t bytes; } copies[] = {
+        {prim_h + first * np, prim, B * np * sizeof(double)}, {dual_h + first * nd, dual, B * nd * sizeof(double)},
+        {obj_h + first, obj, B * sizeof(double)}, {pri_h + first, pri, B * sizeof(double)}, {dua_h + first, dua, B * sizeof(double)},
+        {iter_h + first, iter, B * sizeof(int32_t)}, {status_h + first, status, B * sizeof(int32_t)}};
+    for (const auto &c : copies)
+        if (c.bytes) RT_CHECK(hipMemcpyAsync(c.dst, c.src.p, c.bytes, hipMemcpyDeviceToHost, stream));
     return CPG_OK;
 }
 
@@ -238,6 +282,21 @@ static int build_stream_tables(const int *ctab, const unsigned *desc, const unsi
 #define CPG_MIN_WAVES_PER_SIMD 4   // 16 waves per CU: <= 128 VGPRs
 #endif
 
+// one launch of `kern`: a dynamic LDS size above the 48 KiB default needs the kernel's attribute raised first
+template <typename Kernel, typename... Args>
+static int launch_kernel(Kernel kern, int blocks, int threads, size_t lds, rt_stream_t stream, const Args &...args) {
+    if (lds > 48 * 1024)
+        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, stream, args...);
+    RT_CHECK(hipGetLastError());
+    return CPG_OK;
+}
+// workgroups for `units` work items, `per_wg` to a workgroup, at most `per_cu` workgroups on each CU
+static int grid_blocks(cpg_handle_t h, long long units, int per_wg, long long per_cu) {
+    const long long blocks = (units + per_wg - 1) / per_wg, cap = (long long)h->num_cu * per_cu;
+    return (int)(blocks < cap ? blocks : cap);
+}
+
 // WMAX = waves per workgroup the kernel may be launched with; it fixes the register budget:
 // streaming kernels run several 4-wave workgroups per CU (CPG_MIN_WAVES_PER_SIMD), LDS-resident
 // kernels run ONE workgroup of up to WMAX waves per CU (WMAX / 4 waves per SIMD).
@@ -248,15 +307,6 @@ osqp_shared_kernel(cpg::DevFamily F, cpg::DevUpdate U, cpg::DevSettings S, cpg::
     const int wave_global = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     cpg::osqp_shared_body<NSX, NSZ, NV, G, LDSPROG>(F, U, S, Bt, cpg_lds, wave_global);
 }
-template <int NSX, int NSZ, int NV, int G, bool LDSPROG, int WMAX>
-static int launch_t(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, int waves, size_t lds) {
-    auto kern = osqp_shared_kernel<NSX, NSZ, NV, G, LDSPROG, WMAX>;
-    if (lds > 48 * 1024)
-        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(waves * 64), lds, h->stream, h->F, h->U, h->S, Bt);
-    RT_CHECK(hipGetLastError());
-    return CPG_OK;
-}
 
 template <int NSX, int NSZ, bool SHARED>
 __global__ void __launch_bounds__(256, CPG_REFACTOR_WAVES_PER_SIMD)
@@ -264,15 +314,6 @@ osqp_refactor_kernel(cpg::DevFamily F, cpg::DevRefactor R, cpg::DevSettings S, c
     extern __shared__ __attribute__((aligned(16))) double cpg_lds[];
     const int wave_global = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     cpg::osqp_refactor_body<NSX, NSZ, false, SHARED>(F, R, S, Bt, cpg_lds, wave_global);
-}
-template <int NSX, int NSZ>
-static int launch_refactor_t(cpg_handle_t h, rt_stream_t stream, const cpg::DevSettings &S, const cpg::DevBatch &Bt, int blocks, int waves, size_t lds) {
-    auto kern = h->R.shared_mats ? osqp_refactor_kernel<NSX, NSZ, true> : osqp_refactor_kernel<NSX, NSZ, false>;
-    if (lds > 48 * 1024)
-        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(waves * 64), lds, stream, h->F, h->R, S, Bt);
-    RT_CHECK(hipGetLastError());
-    return CPG_OK;
 }
 #ifdef CPG_REFACTOR_CR_LDS
 // per-instance-matrix kernel with the streaming executor's entry words in LDS (osqp_refactor_body<.., CRLDS>): one
@@ -283,15 +324,6 @@ osqp_refactor_crlds_kernel(cpg::DevFamily F, cpg::DevRefactor R, cpg::DevSetting
     extern __shared__ __attribute__((aligned(16))) double cpg_lds[];
     const int wave_global = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     cpg::osqp_refactor_body<NSX, NSZ, false, false, true>(F, R, S, Bt, cpg_lds, wave_global);
-}
-template <int NSX, int NSZ>
-static int launch_refactor_crlds_t(cpg_handle_t h, rt_stream_t stream, const cpg::DevSettings &S, const cpg::DevBatch &Bt, int blocks, int waves, size_t lds) {
-    auto kern = osqp_refactor_crlds_kernel<NSX, NSZ>;
-    if (lds > 48 * 1024)
-        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(waves * 64), lds, stream, h->F, h->R, S, Bt);
-    RT_CHECK(hipGetLastError());
-    return CPG_OK;
 }
 #endif
 #ifdef CPG_GENI_HEADER
@@ -304,15 +336,6 @@ osqp_instance_kernel(cpg::DevFamily F, cpg::DevRefactor R, cpg::DevSettings S, c
     const int wave_global = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     cpg::osqp_refactor_body<NSX, NSZ, true>(F, R, S, Bt, cpg_lds, wave_global);
 }
-template <int NSX, int NSZ>
-static int launch_instance_t(cpg_handle_t h, rt_stream_t stream, const cpg::DevSettings &S, const cpg::DevBatch &Bt, int blocks, int waves, size_t lds) {
-    auto kern = osqp_instance_kernel<NSX, NSZ>;
-    if (lds > 48 * 1024)
-        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(waves * 64), lds, stream, h->F, h->R, S, Bt);
-    RT_CHECK(hipGetLastError());
-    return CPG_OK;
-}
 #endif
 #ifdef CPG_GENR_HEADER
 // resident per-instance factor kernel (cpg_osqp_resident.h): at most four wavefronts per workgroup and ONE workgroup per
@@ -324,15 +347,6 @@ osqp_resident_kernel(cpg::DevFamily F, cpg::DevRefactor R, cpg::DevResident Rs, 
     const int wave_global = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     cpg::osqp_resident_body<NSX, NSZ>(F, R, Rs, S, Bt, cpg_lds, wave_global);
 }
-template <int NSX, int NSZ>
-static int launch_resident_t(cpg_handle_t h, rt_stream_t stream, const cpg::DevSettings &S, const cpg::DevBatch &Bt, int blocks, int waves, size_t lds) {
-    auto kern = osqp_resident_kernel<NSX, NSZ>;
-    if (lds > 48 * 1024)
-        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(waves * 64), lds, stream, h->F, h->R, h->Rs, S, Bt);
-    RT_CHECK(hipGetLastError());
-    return CPG_OK;
-}
 #endif
 #ifdef CPG_GENT_HEADER
 // team per-instance factor kernel (cpg_osqp_team.h): one workgroup of CPG_GENT_W wavefronts per instance.  Up to four
@@ -342,14 +356,6 @@ osqp_team_kernel(cpg::DevFamily F, cpg::DevRefactor R, cpg::DevResident Rs, cpg:
     extern __shared__ __attribute__((aligned(16))) double cpg_lds[];
     constexpr int NX = (CPG_GENT_N + CPG_GENT_W * 64 - 1) / (CPG_GENT_W * 64), NZ = (CPG_GENT_M + CPG_GENT_W * 64 - 1) / (CPG_GENT_W * 64);
     cpg::osqp_team_body<(NX > 0 ? NX : 1), (NZ > 0 ? NZ : 1)>(F, R, Rs, S, Bt, cpg_lds, (int)blockIdx.x);
-}
-static int launch_team(cpg_handle_t h, rt_stream_t stream, const cpg::DevSettings &S, const cpg::DevBatch &Bt, int blocks, size_t lds) {
-    auto kern = osqp_team_kernel;
-    if (lds > 48 * 1024)
-        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(CPG_GENT_W * 64), lds, stream, h->F, h->R, h->Rs, S, Bt);
-    RT_CHECK(hipGetLastError());
-    return CPG_OK;
 }
 #endif
 #ifdef CPG_GENQ_HEADER
@@ -361,18 +367,6 @@ osqp_squad_kernel(cpg::DevFamily F, cpg::DevUpdate U, cpg::DevSettings S, cpg::D
     extern __shared__ __attribute__((aligned(16))) double cpg_lds[];
     cpg::osqp_squad_body<NSX, NSZ, NV>(F, U, S, Bt, cpg_lds);
 }
-template <int NSX, int NSZ, int NV>
-static int launch_squad_t(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, size_t lds) {
-    auto kern = osqp_squad_kernel<NSX, NSZ, NV>;
-    if (lds > 48 * 1024)
-        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(CPG_GENQ_W * 64), lds, h->stream, h->F, h->U, h->S, Bt);
-    RT_CHECK(hipGetLastError());
-    return CPG_OK;
-}
-#endif
-#ifndef CPG_KERNELS_REFACTOR
-#define CPG_KERNELS_REFACTOR(Z) Z(1, 1) Z(4, 4) Z(8, 8) Z(16, 16)
 #endif
 template <int NSX, int NSZ>
 __global__ void __launch_bounds__(512, CPG_GRADIENT_WAVES_PER_SIMD)
@@ -381,32 +375,42 @@ osqp_gradient_kernel(cpg::DevFamily F, cpg::DevRefactor R, cpg::DevGradient Gd, 
     const int wave_global = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     cpg::osqp_gradient_body<NSX, NSZ>(F, R, Gd, Bt, cpg_lds, wave_global);
 }
-template <int NSX, int NSZ>
-static int launch_gradient_t(cpg_handle_t h, const cpg::DevGradBatch &Bt, int blocks, int waves, size_t lds) {
-    auto kern = osqp_gradient_kernel<NSX, NSZ>;
-    if (lds > 48 * 1024)
-        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(waves * 64), lds, h->stream, h->F, h->R, h->Gd, Bt);
-    RT_CHECK(hipGetLastError());
-    return CPG_OK;
-}
-static int launch_gradient(cpg_handle_t h, const cpg::DevGradBatch &Bt, int blocks, int waves, size_t lds) {
+
+// Slot classes (ceil(n/64), ceil(m/64)) of the per-instance factor and adjoint kernels.  slot_class calls
+// launch(NSX, NSZ) -- std::integral_constant's -- with the first compiled class that covers the family and
+// returns true, or returns false when none does; with_slot_class makes the latter an error.
+#ifndef CPG_KERNELS_REFACTOR
+#define CPG_KERNELS_REFACTOR(Z) Z(1, 1) Z(4, 4) Z(8, 8) Z(16, 16)
+#endif
+template <typename Launch>
+static bool slot_class(cpg_handle_t h, int &rc, Launch &&launch) {
     const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64;
-#define Z(a, b) if (nsx <= a && nsz <= b) return launch_gradient_t<a, b>(h, Bt, blocks, waves, lds);
+#define Z(a, b)                                                                                   \
+    if (nsx <= a && nsz <= b) {                                                                   \
+        rc = launch(std::integral_constant<int, a>(), std::integral_constant<int, b>());          \
+        return true;                                                                              \
+    }
     CPG_KERNELS_REFACTOR(Z)
 #undef Z
+    return false;
+}
+template <typename Launch>
+static int with_slot_class(cpg_handle_t h, Launch &&launch) {
+    int rc;
+    if (slot_class(h, rc, launch)) return rc;
     set_error("problem family larger than the largest compiled slot class");
     return CPG_E_UNSUPPORTED;
+}
+static int launch_gradient(cpg_handle_t h, const cpg::DevGradBatch &Bt, int blocks, int waves, size_t lds) {
+    return with_slot_class(h, [&](auto NSX, auto NSZ) {
+        return launch_kernel(osqp_gradient_kernel<NSX, NSZ>, blocks, waves * 64, lds, h->stream, h->F, h->R, h->Gd, Bt); });
 }
 // (stream and settings are the caller's: the hand-over launch of a linked handle runs on the shared-factor
 // handle's stream with that handle's settings)
 static int launch_refactor(cpg_handle_t h, rt_stream_t stream, const cpg::DevSettings &S, const cpg::DevBatch &Bt, int blocks, int waves, size_t lds) {
-    const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64;
-#define Z(a, b) if (nsx <= a && nsz <= b) return launch_refactor_t<a, b>(h, stream, S, Bt, blocks, waves, lds);
-    CPG_KERNELS_REFACTOR(Z)
-#undef Z
-    set_error("problem family larger than the largest compiled slot class");
-    return CPG_E_UNSUPPORTED;
+    return with_slot_class(h, [&](auto NSX, auto NSZ) {
+        return launch_kernel(h->R.shared_mats ? osqp_refactor_kernel<NSX, NSZ, true> : osqp_refactor_kernel<NSX, NSZ, false>,
+                             blocks, waves * 64, lds, stream, h->F, h->R, S, Bt); });
 }
 
 // ---- conic interior-point kernel: no slot classes, every vector lives in LDS ---------------------
@@ -420,26 +424,18 @@ clarabel_kernel(cpg::DevConic C, cpg::DevConicSettings S, cpg::DevBatch Bt) {
     const int wave_global = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     cpg::clarabel_body<TABLES_IN_LDS, SPECIALISED, NONSYM>(C, S, Bt, cpg_lds, wave_global);
 }
-// NONSYM: families with exponential / power cones run an instantiation of their own -- the symmetric kernel carries none of that code
-template <bool TABLES_IN_LDS, bool SPECIALISED, bool NONSYM = false>
-static int launch_conic_t(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, int waves, size_t lds) {
-    auto kern = clarabel_kernel<TABLES_IN_LDS, SPECIALISED, NONSYM>;
-    if (lds > 48 * 1024)
-        RT_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(waves * 64), lds, h->stream, h->C, h->CS, Bt);
-    RT_CHECK(hipGetLastError());
-    return CPG_OK;
-}
+// NONSYM: families with exponential / power / PSD cones run an instantiation of their own -- the symmetric kernel carries none of that code
 static int launch_conic(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, int waves, size_t lds, bool tables_in_lds) {
-    const bool extended = h->C.n_ns > 0 || h->C.n_psd > 0;       // exponential / power / PSD cones: the instantiation that carries their code
+    const bool extended = h->C.n_ns > 0 || h->C.n_psd > 0;
 #ifdef CPG_GENC_HEADER
     // the library's own family: dimensions as compile-time constants (clarabel_body<., true>)
     if (h->conic_specialised && tables_in_lds)
-        return extended ? launch_conic_t<true, true, true>(h, Bt, blocks, waves, lds) : launch_conic_t<true, true>(h, Bt, blocks, waves, lds);
+        return launch_kernel(extended ? clarabel_kernel<true, true, true> : clarabel_kernel<true, true, false>,
+                             blocks, waves * 64, lds, h->stream, h->C, h->CS, Bt);
 #endif
-    if (extended)
-        return tables_in_lds ? launch_conic_t<true, false, true>(h, Bt, blocks, waves, lds) : launch_conic_t<false, false, true>(h, Bt, blocks, waves, lds);
-    return tables_in_lds ? launch_conic_t<true, false>(h, Bt, blocks, waves, lds) : launch_conic_t<false, false>(h, Bt, blocks, waves, lds);
+    auto kern = extended ? (tables_in_lds ? clarabel_kernel<true, false, true> : clarabel_kernel<false, false, true>)
+                         : (tables_in_lds ? clarabel_kernel<true, false, false> : clarabel_kernel<false, false, false>);
+    return launch_kernel(kern, blocks, waves * 64, lds, h->stream, h->C, h->CS, Bt);
 }
 
 
@@ -460,20 +456,23 @@ static int launch_conic(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, int
     Y(16, 16, 16, 1, 8)
 #endif
 
-static int launch(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, int waves, int G, size_t lds, bool in_lds) {
-    const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64;
+// slots with per-instance q / u (the NV a kernel must cover)
+static int vary_slots(cpg_handle_t h) {
     const int nvx = (h->n_vary_x + 63) / 64, nvz = (h->n_vary_z + 63) / 64;
-    const int nv = nvx > nvz ? nvx : nvz;
+    return nvx > nvz ? nvx : nvz;
+}
+static int launch(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, int waves, int G, size_t lds, bool in_lds) {
+    const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64, nv = vary_slots(h);
     if (!in_lds) {
 #define X(a, b, v, g)                                                                             \
         if (nsx <= a && nsz <= b && (nv <= v || (v >= a && v >= b)) && G == g && waves <= 4)      \
-            return launch_t<a, b, v, g, false, 4>(h, Bt, blocks, waves, lds);
+            return launch_kernel(osqp_shared_kernel<a, b, v, g, false, 4>, blocks, waves * 64, lds, h->stream, h->F, h->U, h->S, Bt);
         CPG_KERNELS(X)
 #undef X
     } else {
 #define Y(a, b, v, g, wm)                                                                         \
         if (nsx <= a && nsz <= b && (nv <= v || (v >= a && v >= b)) && G == g && waves <= wm)     \
-            return launch_t<a, b, v, g, true, wm>(h, Bt, blocks, waves, lds);
+            return launch_kernel(osqp_shared_kernel<a, b, v, g, true, wm>, blocks, waves * 64, lds, h->stream, h->F, h->U, h->S, Bt);
         CPG_KERNELS_LDS(Y)
 #undef Y
     }
@@ -483,18 +482,318 @@ static int launch(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, int waves
 
 #ifdef CPG_GENQ_HEADER
 static int launch_squad(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, size_t lds) {
-    const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64;
-    const int nvx = (h->n_vary_x + 63) / 64, nvz = (h->n_vary_z + 63) / 64;
-    const int nv = nvx > nvz ? nvx : nvz;
+    const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64, nv = vary_slots(h);
 #define Y(a, b, v, g, wm)                                                                         \
     if (nsx == a && nsz == b && (nv <= v || (v >= a && v >= b)) && g == 1)                        \
-        return launch_squad_t<a, b, v>(h, Bt, blocks, lds);
+        return launch_kernel(osqp_squad_kernel<a, b, v>, blocks, CPG_GENQ_W * 64, lds, h->stream, h->F, h->U, h->S, Bt);
     CPG_KERNELS_LDS(Y)
 #undef Y
     set_error("no compiled squad kernel for this family size");
     return CPG_E_UNSUPPORTED;
 }
 #endif
+
+// ------------------------------------------------------------------------------------ solve dispatch
+static cpg::DevBatch make_batch(int64_t B, const double *d_theta, const double *d_state_in, double *d_state_out, double *d_prim,
+                                double *d_dual, double *d_obj, int32_t *d_iter, int32_t *d_status, double *d_pri, double *d_dua) {
+    cpg::DevBatch Bt;
+    Bt.scratch = nullptr; Bt.state_in = d_state_in; Bt.state_out = d_state_out;
+    Bt.B = B; Bt.theta = d_theta; Bt.prim = d_prim; Bt.dual = d_dual; Bt.obj = d_obj; Bt.pri_res = d_pri;
+    Bt.dua_res = d_dua; Bt.iter = d_iter; Bt.status = d_status; Bt.counter = nullptr;
+    Bt.ho_list = nullptr; Bt.ho_count = nullptr; Bt.ho_state = nullptr; Bt.list = nullptr; Bt.list_count = nullptr; Bt.resume = 0;
+    return Bt;
+}
+
+// per-instance factor kernel of handle `h` (its tables, its scratch) on `stream` with settings `S`
+static int launch_per_instance(cpg_handle_t h, rt_stream_t stream, const cpg::DevSettings &S, cpg::DevBatch &Bt) {
+    int rc;
+    // `doubles` of scratch for each wavefront of the launch
+    auto scratch = [&](int blocks, int waves, size_t doubles) {
+        const int r = ensure(h->scratch, (size_t)blocks * waves * doubles * sizeof(double));
+        Bt.scratch = (double *)h->scratch.p;
+        return r;
+    };
+#ifdef CPG_GENT_HEADER
+    if (h->Rs.ok == 2 && !h->R.shared_mats && h->program_in_lds != 0 && h->program_in_lds != 2) {
+        // team kernel: one instance per workgroup; as many workgroups per CU as their LDS (scratch + slice) allows
+        const size_t lds = ((size_t)CPG_TEAM_SLICE_OFF + (size_t)h->Rs.slice_doubles) * sizeof(double);
+        if (lds <= h->lds_limit) {
+            long long per_cu = (long long)(h->lds_limit / lds);
+            if (per_cu * CPG_GENT_W > 16) per_cu = 16 / CPG_GENT_W;
+            if (CPG_GENT_W <= 4 && per_cu * CPG_GENT_W > 4) per_cu = 4 / CPG_GENT_W;       // (kernels built for one wavefront per SIMD)
+            if (h->blocks_per_cu > 0 && per_cu > h->blocks_per_cu) per_cu = h->blocks_per_cu;
+            const int blocks = std::max(1, grid_blocks(h, Bt.B, 1, per_cu));
+            if ((rc = scratch(blocks, 1, h->Rs.buf_doubles))) return rc;
+            return launch_kernel(osqp_team_kernel, blocks, CPG_GENT_W * 64, lds, stream, h->F, h->R, h->Rs, S, Bt);
+        }
+    }
+#endif
+#ifdef CPG_GENR_HEADER
+    if (h->Rs.ok && !h->R.shared_mats && h->program_in_lds != 0 && h->program_in_lds != 2) {
+        // resident kernel: one workgroup per CU, as many wavefronts (<= 4: one per SIMD) as slices fit the LDS
+#ifdef CPG_GENR_TABLES_GLOBAL
+        const size_t tab = 0;                          // (the executor's tables stay in global memory)
+#else
+        const size_t tab = (size_t)(((CPG_GENR_NSTEPS + 3) / 4) * 256 + ((CPG_GENR_NCHUNKS + 3) / 4) * 256) * sizeof(unsigned short);
+#endif
+        const size_t slice = (size_t)h->Rs.slice_doubles * sizeof(double);
+        int NW = h->waves_per_block > 0 ? h->waves_per_block : 4;
+        if (NW > 4) NW = 4;
+        while (NW > 1 && tab + (size_t)NW * slice > h->lds_limit) NW--;
+        const size_t lds = tab + (size_t)NW * slice;
+        if (lds <= h->lds_limit) {
+            const int blocks = grid_blocks(h, Bt.B, NW, 1);
+            if ((rc = scratch(blocks, NW, h->Rs.buf_doubles))) return rc;
+            if (slot_class(h, rc, [&](auto NSX, auto NSZ) {
+                    return launch_kernel(osqp_resident_kernel<NSX, NSZ>, blocks, NW * 64, lds, stream, h->F, h->R, h->Rs, S, Bt); }))
+                return rc;
+        }
+    }
+#endif
+#ifdef CPG_GENI_HEADER
+    if (h->R.gi_ok && h->program_in_lds != 0 && h->program_in_lds != 2) {
+        const int W = 8;                               // one workgroup of eight wavefronts per CU shares the tables       // generated instance executor (cpg_hip_set_program_placement(0): the streaming one)
+        const size_t tab = (size_t)(((CPG_GENI_NSTEPS + 3) / 4) * 256 + ((CPG_GENI_NCHUNKS + 3) / 4) * 256) * sizeof(unsigned short);
+        const size_t nq = (size_t)(h->F.n + h->F.m);
+        size_t per_wave = (size_t)(CPG_GENI_NSLOTS + CPG_GEN_EXTRA_SLOTS) + nq + (nq & 1);   // work vector | q | u ...
+#ifdef CPG_GENI_FAC_NSTEPS
+        const size_t fac = (size_t)h->R.nnzL + nq + 1;                                        // ... or the factor (+ a zero slot) while it is computed
+#else
+        const size_t fac = (size_t)h->R.nnzL + nq;                                            // ... or the factor while it is computed
+#endif
+        if (per_wave < fac) per_wave = fac + (fac & 1);
+        const size_t lds = tab + (size_t)W * per_wave * sizeof(double);
+        if (lds <= h->lds_limit) {
+            const int blocks = grid_blocks(h, Bt.B, W, 1);   // 8 wavefronts per CU: the register budget of the kernel
+            if ((rc = scratch(blocks, W, h->R.buf_doubles))) return rc;
+            if (slot_class(h, rc, [&](auto NSX, auto NSZ) {
+                    return launch_kernel(osqp_instance_kernel<NSX, NSZ>, blocks, W * 64, lds, stream, h->F, h->R, S, Bt); }))
+                return rc;
+        }
+    }
+#endif
+#ifdef CPG_REFACTOR_CR_LDS
+    if (!h->R.shared_mats && h->program_in_lds != 0) {       // (cpg_hip_set_program_placement(0): entry words through L2, as before)
+        const int W8 = 8;
+        const size_t tab = (((size_t)h->R.sol_nnz + 1) / 2) * sizeof(double);
+        const size_t lds8 = tab + (size_t)W8 * h->R.sol_slots * sizeof(double);
+        if (lds8 <= h->lds_limit) {
+            const int blocks = grid_blocks(h, Bt.B, W8, 1);
+            if ((rc = scratch(blocks, W8, h->R.buf_doubles))) return rc;
+            if (slot_class(h, rc, [&](auto NSX, auto NSZ) {
+                    return launch_kernel(osqp_refactor_crlds_kernel<NSX, NSZ>, blocks, W8 * 64, lds8, stream, h->F, h->R, S, Bt); }))
+                return rc;
+        }
+    }
+#endif
+    const int W = 4;
+#ifdef CPG_GENS_HEADER
+    if (!h->R.shared_mats && !h->R.gs_ok) {
+        set_error("this library's per-instance substitution program was generated for a different family"); return CPG_E_BADARG; }
+    const size_t lds = (size_t)W * (size_t)(h->R.shared_mats ? h->R.sol_slots : h->R.sol_slots + CPG_GEN_EXTRA_SLOTS) * sizeof(double);
+#else
+    const size_t lds = (size_t)W * h->R.sol_slots * sizeof(double);
+#endif
+    if (lds > h->lds_limit) { set_error("work vectors do not fit the LDS"); return CPG_E_UNSUPPORTED; }
+    int per_cu = h->blocks_per_cu > 0 ? h->blocks_per_cu : CPG_REFACTOR_WAVES_PER_SIMD;    // workgroups of 4 waves
+    if (per_cu > CPG_REFACTOR_WAVES_PER_SIMD) per_cu = CPG_REFACTOR_WAVES_PER_SIMD;
+    if ((long long)per_cu * (long long)lds > (long long)h->lds_limit) per_cu = (int)(h->lds_limit / lds);
+    const int blocks = grid_blocks(h, Bt.B, W, per_cu);
+    if ((rc = scratch(blocks, W, h->R.buf_doubles))) return rc;
+    return launch_refactor(h, stream, S, Bt, blocks, W, lds);
+}
+
+// A solve's launches sit between begin_solve (the counters d_counter[0..3] cleared, ev0) and end_solve (ev1):
+// cpg_hip_last_kernel_ms and cpg_hip_last_phase_ms time them.  (The conic kernel uses d_counter[0] only.)
+static int begin_solve(cpg_handle_t h) {
+    RT_CHECK(hipMemsetAsync(h->d_counter, 0, 4 * sizeof(unsigned), h->stream));
+    RT_CHECK(hipEventRecord(h->ev0, h->stream));
+    return CPG_OK;
+}
+static int end_solve(cpg_handle_t h) {
+    RT_CHECK(hipEventRecord(h->ev1, h->stream));
+    return CPG_OK;
+}
+
+// interior-point handle
+static int solve_conic(cpg_handle_t h, const cpg::DevBatch &Bt) {
+    const size_t per_wave = (size_t)h->C.lds_doubles * sizeof(double);
+    // the kernel is compiled for CPG_CONIC_WAVES_PER_SIMD waves per SIMD (register budget).  The
+    // family's index tables get a block-shared LDS copy whenever a workgroup still fits; measured
+    // best on MI355X (ADP): workgroups of 8 waves (15.8 ms; 17.3 with 7, 19.4 with 6).
+    int W = h->waves_per_block > 0 ? (h->waves_per_block > 8 ? 8 : h->waves_per_block) : 8;
+    const size_t tab = (size_t)h->C.tab_doubles * sizeof(double);
+    const bool tables_in_lds = h->program_in_lds != 0 && tab + per_wave <= h->lds_limit;
+    const size_t fixed = tables_in_lds ? tab : 0;
+    while (W > 1 && fixed + (size_t)W * per_wave > h->lds_limit) W--;
+    if (h->waves_per_block <= 0) {
+        // what counts is the number of resident waves per CU (the kernel is VALU-issue bound from ~12 on): when a
+        // second 8-wave workgroup just misses the LDS, two smaller ones beat one (ADP with the previous-iterate
+        // copy: 8 + 0 waves at 83.8 KB per workgroup, 7 + 7 at 75.1 KB)
+        int best = W, best_res = 0;
+        for (int w2 = W; w2 >= 4; w2--) {
+            int pc = (int)(h->lds_limit / (fixed + (size_t)w2 * per_wave));
+            if (h->blocks_per_cu > 0 && pc > h->blocks_per_cu) pc = h->blocks_per_cu;
+            int res = pc * w2; if (res > 4 * CPG_CONIC_WAVES_PER_SIMD) res = 4 * CPG_CONIC_WAVES_PER_SIMD;
+            if (res > best_res) { best_res = res; best = w2; }
+        }
+        W = best;
+    }
+    // (+ 16 doubles behind the last wavefront's slice: the specialised kernel's per-cone loops are unrolled to the family's largest
+    // cone and load past the end of a shorter trailing cone before they mask the use -- inside the allocation with this pad)
+    const size_t lds = fixed + (size_t)W * per_wave + (fixed + (size_t)W * per_wave + 128 <= h->lds_limit ? 128 : 0);
+    int per_cu = (int)(h->lds_limit / lds); if (per_cu < 1) per_cu = 1;
+    if (h->blocks_per_cu > 0 && per_cu > h->blocks_per_cu) per_cu = h->blocks_per_cu;
+    if (per_cu * W > 4 * CPG_CONIC_WAVES_PER_SIMD) per_cu = (4 * CPG_CONIC_WAVES_PER_SIMD) / W;
+    if (per_cu < 1) per_cu = 1;
+    const int blocks = grid_blocks(h, Bt.B, W, per_cu);
+    int rc;
+    if ((rc = begin_solve(h)) || (rc = launch_conic(h, Bt, blocks, W, lds, tables_in_lds))) return rc;
+    return end_solve(h);
+}
+
+// OSQP handle with per-instance factor tables (cpg_hip_set_refactor)
+static int solve_per_instance(cpg_handle_t h, cpg::DevBatch &Bt) {
+    int rc;
+    if ((rc = begin_solve(h)) || (rc = launch_per_instance(h, h->stream, h->S, Bt))) return rc;
+    h->two_phase_last = false;
+    return end_solve(h);
+}
+
+// The launches of a shared-factor solve: `launch` (the squad or the table-driven kernel) and, when two_phase, the
+// hybrid hand-over behind it -- the instances whose rho changes go on in the linked handle's per-instance factor
+// kernel, on this handle's stream with its settings.
+template <typename Launch>
+static int shared_launches(cpg_handle_t h, cpg::DevBatch &Bt, bool two_phase, Launch &&launch) {
+    int rc;
+    if (two_phase) {
+        // hand-over buffers: the workspace of every instance whose rho changes (the caller's state_out rows serve
+        // when it gave a buffer: the continuing kernel overwrites them with the final workspace) and their numbers
+        const size_t state_bytes = (size_t)Bt.B * ((size_t)h->F.n + 2 * (size_t)h->F.m + 1) * sizeof(double);
+        if (!Bt.state_out && (rc = ensure(h->ho_state, state_bytes))) return rc;
+        if ((rc = ensure(h->ho_list, (size_t)Bt.B * sizeof(int)))) return rc;
+        Bt.ho_state = Bt.state_out ? Bt.state_out : (double *)h->ho_state.p;
+        Bt.ho_list = (int *)h->ho_list.p; Bt.ho_count = h->d_counter + 1;
+    }
+    if ((rc = begin_solve(h)) || (rc = launch(Bt))) return rc;
+    h->two_phase_last = two_phase;
+    if (two_phase) {
+        RT_CHECK(hipEventRecord(h->ev_mid, h->stream));
+        cpg::DevBatch B2 = make_batch(Bt.B, Bt.theta, Bt.ho_state, Bt.state_out, Bt.prim, Bt.dual, Bt.obj, Bt.iter, Bt.status,
+                                      Bt.pri_res, Bt.dua_res);
+        B2.counter = h->d_counter + 2; B2.list = Bt.ho_list; B2.list_count = h->d_counter + 1; B2.resume = 1;
+        if ((rc = launch_per_instance(h->linked, h->stream, h->S, B2))) return rc;
+    }
+    return end_solve(h);
+}
+
+// OSQP handle with the shared factor
+static int solve_shared(cpg_handle_t h, cpg::DevBatch &Bt) {
+    // rho adaptation on the shared factor: hybrid execution when a per-instance factor handle is linked
+    // (cpg_hip_set_handover); without one the kernel flags the instances whose rho changes (status -2) and the
+    // host layer re-solves them through the per-instance factor path
+    const bool two_phase = h->S.adaptive_rho && h->S.adaptive_rho_interval > 0 && h->linked != nullptr;
+    if (h->S.adaptive_rho && h->S.adaptive_rho_interval > 0 && h->linked == nullptr && !h->flag_rho_changes) {
+        // a shared factor cannot follow a rho change: without a linked per-instance factor handle every instance whose rho
+        // estimate leaves the tolerance band would come back UNSOLVED under the internal status -2 -- refuse instead
+        set_error("rho adaptation is on and this shared-factor handle has no per-instance factor handle linked (cpg_hip_set_handover): "
+                  "link one, or turn it off (cpg_hip_set_build_option(h, \"adaptive_rho\", 0)), or accept instances flagged "
+                  "CPG_STATUS_NEEDS_REFACTOR (-2) with cpg_hip_set_build_option(h, \"flag_rho_changes\", 1)");
+        return CPG_E_UNSUPPORTED;
+    }
+    if (two_phase && !h->linked->refactor_mode) { set_error("linked handle has no per-instance factor tables (cpg_hip_set_refactor)"); return CPG_E_BADARG; }
+    const int G = h->inst_per_wave;
+    const size_t N = (size_t)(h->F.n + h->F.m);
+#ifdef CPG_GENQ_HEADER
+    if (h->squad_ok && G == 1 && h->program_in_lds == 3) {
+        // squad executor (on request: it lost the A/B against the LDS-resident program on MI355X, HISTORY.md round 6): CPG_GENQ_W
+        // instances per workgroup of CPG_GENQ_W wavefronts, the program in their registers
+        const size_t lds_q = cpg::squad_lds_bytes((unsigned)h->F.n, (unsigned)h->F.m);
+        if (lds_q > h->lds_limit) { set_error("the squad executor's LDS need exceeds the device limit"); return CPG_E_UNSUPPORTED; }
+        int per_cu = (int)(h->lds_limit / lds_q);
+        const int by_regs = 8 / CPG_GENQ_W > 0 ? 8 / CPG_GENQ_W : 1;     // two wavefronts per SIMD
+        if (per_cu > by_regs) per_cu = by_regs;
+        if (h->blocks_per_cu > 0 && per_cu > h->blocks_per_cu) per_cu = h->blocks_per_cu;
+        const int blocks = grid_blocks(h, Bt.B, CPG_GENQ_W, per_cu);
+        return shared_launches(h, Bt, two_phase, [&](const cpg::DevBatch &b) { return launch_squad(h, b, blocks, lds_q); });
+    }
+#endif
+    if (h->program_in_lds == 3) { set_error("this library carries no squad executor for the family (cpg_hip_set_program_placement(3))"); return CPG_E_UNSUPPORTED; }
+#if defined(CPG_GEN_HEADER) && defined(CPG_GEN_N)
+    const size_t per_wave = (size_t)G * (h->F.n_slots + CPG_GEN_EXTRA_SLOTS) * sizeof(double);
+#else
+    const size_t per_wave = (size_t)G * h->F.n_slots * sizeof(double);
+#endif
+    // LDS-resident program: one workgroup per CU, as many waves as fit next to the program
+    const cpg::DevRagged &R = h->F.kkt_ragged;
+#ifdef CPG_GEN_HEADER
+    const size_t tab_doubles = (size_t)((R.n_chunks + 3) & ~3) * 16;     // 16-bit output-slot table, four chunks per entry group
+#else
+    const size_t tab_doubles = (size_t)R.n_chunks * 34;     // desc (u32 x 64) + ctab (int x 4)
+#endif
+#ifdef CPG_GEN_HEADER
+    const size_t nnzp = (size_t)R.nnz + CPG_GEN_PAD;
+#else
+    const size_t nnzp = (size_t)R.nnz;
+#endif
+#ifdef CPG_GEN_COMPRESSED
+    const size_t prog_bytes = R.n_chunks > 0 ? ((size_t)R.n_dict + (nnzp + 1) / 2 + tab_doubles) * 8 : 0;
+#else
+#ifdef CPG_GEN_PADDED_OFFSETS
+    const size_t n_off = (size_t)64 * ((CPG_GEN_PADDED_OFFSETS + 3) & ~3);    // operand offsets of all 64 lanes of every step
+#else
+    const size_t n_off = nnzp;
+#endif
+    const size_t prog_bytes = R.n_chunks > 0 ? (nnzp + (n_off + 3) / 4 + tab_doubles) * 8 : 0;
+#endif
+    bool in_lds = false;
+    int W = h->waves_per_block;
+    // table-driven kernels, automatic placement: the streaming executor (program through L2, operands
+    // of eight steps in flight, more resident waves) beats the LDS-resident table walk -- 1.44 M vs
+    // 1.10 M instances/s on MPC 12/4/10; the LDS-resident form remains for G = 2 and on request
+    const int placement = h->program_in_lds == 2 ? -1 : h->program_in_lds;     // (2 concerns per-instance factor handles only)
+#ifdef CPG_GEN_HEADER
+    const bool prefer_stream = false;   // family library: the generated executor works on the LDS-resident program
+#else
+    const bool prefer_stream = placement == -1 && G == 1 && h->F.kkt_stream.n_pairs > 0;
+#endif
+    if (placement != 0 && R.n_chunks > 0 && !prefer_stream) {
+        const size_t fixed = N * 8 + prog_bytes;
+        int wfit = fixed < h->lds_limit ? (int)((h->lds_limit - fixed) / per_wave) : 0;
+        // every slot class has an LDS kernel for <= 8 waves (<= 4 for G = 2 on the larger classes);
+        // more waves only on explicit request (cpg_hip_set_launch) where such a kernel exists
+        int wcap = h->waves_per_block > 0 ? 16 : (G == 2 ? 4 : 8);
+#ifdef CPG_GEN_HEADER
+        if (h->waves_per_block <= 0) {   // family library: as many waves as its widest compiled kernel admits
+            const int nsx_ = (h->F.n + 63) / 64, nsz_ = (h->F.m + 63) / 64;
+#define Y(a, b, v, g, wm) if (nsx_ <= a && nsz_ <= b && G == g && wm > wcap) wcap = wm;
+            CPG_KERNELS_LDS(Y)
+#undef Y
+        }
+#endif
+        if (wfit > wcap) wfit = wcap;
+        if (wfit >= 4 || (placement == 1 && wfit >= 1)) {
+            in_lds = true;
+            if (W <= 0 || W > wfit) W = wfit;
+        } else if (placement == 1) {
+            set_error("solve program does not fit into LDS next to the work vectors"); return CPG_E_UNSUPPORTED;
+        }
+    }
+    if (!in_lds && (W <= 0 || W > 4)) W = 4;
+    const size_t lds = N * 8 + (in_lds ? prog_bytes : 0) + (size_t)W * per_wave;
+    if (lds > h->lds_limit) { set_error("work vectors do not fit the 160 KiB LDS; lower waves_per_block / inst_per_wave"); return CPG_E_UNSUPPORTED; }
+    const long long ngroups = (Bt.B + G - 1) / G;
+    int per_cu = h->blocks_per_cu;
+    if (in_lds) per_cu = 1;
+    else if (per_cu <= 0) {   // as many blocks as LDS and the register budget (CPG_MIN_WAVES_PER_SIMD) admit
+        per_cu = (int)(h->lds_limit / (lds ? lds : 1));
+        const int by_regs = (CPG_MIN_WAVES_PER_SIMD * 4) / W;
+        if (per_cu > by_regs) per_cu = by_regs;
+        if (per_cu < 1) per_cu = 1;
+    }
+    const int blocks = grid_blocks(h, ngroups, W, per_cu);
+    return shared_launches(h, Bt, two_phase, [&](const cpg::DevBatch &b) { return launch(h, b, blocks, W, G, lds, in_lds); });
+}
 
 // ------------------------------------------------------------------------------------ C-ABI
 extern "C" {
@@ -1169,11 +1468,9 @@ int cpg_hip_create_clarabel(const cpg_conic_family_t *f, int device, cpg_handle_
     return CPG_OK;
 }
 
-static int ensure(DevBuf &b, size_t bytes);
 struct cpg_pipe_s;
 static void free_pipe(cpg_pipe_s *p);
 static void free_list(std::vector<void *> &v) { for (void *p : v) rt_free(p); v.clear(); }
-static void free_buf(DevBuf &b) { if (b.p) rt_free(b.p); b.p = nullptr; b.bytes = 0; }
 
 int cpg_hip_destroy(cpg_handle_t h) {
     if (!h) return CPG_OK;
@@ -1183,9 +1480,7 @@ int cpg_hip_destroy(cpg_handle_t h) {
     free_buf(h->g_theta); free_buf(h->g_x); free_buf(h->g_y); free_buf(h->g_dprim); free_buf(h->g_dtheta);
     if (h->d_counter) rt_free(h->d_counter);
     free_buf(h->scratch);
-    free_buf(h->s_theta); free_buf(h->s_prim); free_buf(h->s_dual); free_buf(h->s_obj);
-    free_buf(h->s_pri); free_buf(h->s_dua); free_buf(h->s_iter); free_buf(h->s_status);
-    free_buf(h->s_state_in); free_buf(h->s_state_out);
+    free_buf(h->s_theta); h->s_out.free(); free_buf(h->s_state_in); free_buf(h->s_state_out);
     free_buf(h->ho_state); free_buf(h->ho_list);
     free_pipe(h->pipe); h->pipe = nullptr;
     if (h->have_events) { hipEventDestroy(h->ev0); hipEventDestroy(h->ev1); hipEventDestroy(h->ev_mid); }
@@ -2030,9 +2325,7 @@ int cpg_hip_gradient_batch(cpg_handle_t h, int64_t B, const double *theta, const
         if (pc >= 1 && pc * w > per_cu * W) { W = w; per_cu = pc; }
     }
     const size_t lds = (size_t)W * per_wave * sizeof(double);
-    long long blocks = (B + W - 1) / W;
-    const long long cap = (long long)h->num_cu * per_cu;
-    if (blocks > cap) blocks = cap;
+    const int blocks = grid_blocks(h, B, W, per_cu);
     if ((rc = ensure(h->scratch, (size_t)blocks * W * (size_t)h->R.buf_doubles * sizeof(double)))) return rc;
     cpg::DevGradBatch Bt;
     Bt.B = B; Bt.theta = (const double *)h->g_theta.p; Bt.sol_x = (const double *)h->g_x.p;
@@ -2040,7 +2333,7 @@ int cpg_hip_gradient_batch(cpg_handle_t h, int64_t B, const double *theta, const
     Bt.counter = h->d_counter; Bt.scratch = (double *)h->scratch.p;
     RT_CHECK(hipMemsetAsync(h->d_counter, 0, sizeof(unsigned), h->stream));
     RT_CHECK(hipEventRecord(h->ev0, h->stream));
-    rc = launch_gradient(h, Bt, (int)blocks, W, lds);
+    rc = launch_gradient(h, Bt, blocks, W, lds);
     if (rc) return rc;
     RT_CHECK(hipEventRecord(h->ev1, h->stream));
     if ((rc = rt_d2h(h, dtheta, h->g_dtheta.p, b * h->Gd.NP * sizeof(double)))) return rc;
@@ -2057,367 +2350,36 @@ int cpg_hip_set_launch(cpg_handle_t h, int waves_per_block, int inst_per_wave, i
     return CPG_OK;
 }
 
-static int ensure(DevBuf &b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return CPG_OK;
-    if (b.p) rt_free(b.p);
-    b.p = nullptr; b.bytes = 0;
-    int rc = rt_malloc(&b.p, bytes);
-    if (rc) return rc;
-    b.bytes = bytes;
-    return CPG_OK;
-}
-
 int cpg_hip_set_program_placement(cpg_handle_t h, int in_lds) {
     if (!h || in_lds < -1 || in_lds > 3) { set_error("in_lds must be -1, 0, 1, 2 or 3"); return CPG_E_BADARG; }
     h->program_in_lds = in_lds;
     return CPG_OK;
 }
 
-static cpg::DevBatch make_batch(int64_t B, const double *d_theta, const double *d_state_in, double *d_state_out, double *d_prim,
-                                double *d_dual, double *d_obj, int32_t *d_iter, int32_t *d_status, double *d_pri, double *d_dua) {
-    cpg::DevBatch Bt;
-    Bt.scratch = nullptr; Bt.state_in = d_state_in; Bt.state_out = d_state_out;
-    Bt.B = B; Bt.theta = d_theta; Bt.prim = d_prim; Bt.dual = d_dual; Bt.obj = d_obj; Bt.pri_res = d_pri;
-    Bt.dua_res = d_dua; Bt.iter = d_iter; Bt.status = d_status; Bt.counter = nullptr;
-    Bt.ho_list = nullptr; Bt.ho_count = nullptr; Bt.ho_state = nullptr; Bt.list = nullptr; Bt.list_count = nullptr; Bt.resume = 0;
-    return Bt;
-}
-
-// per-instance factor kernel of handle `h` (its tables, its scratch) on `stream` with settings `S`
-static int launch_per_instance(cpg_handle_t h, rt_stream_t stream, const cpg::DevSettings &S, cpg::DevBatch &Bt) {
-    const int W = 4;
-#ifdef CPG_GENT_HEADER
-    if (h->Rs.ok == 2 && !h->R.shared_mats && h->program_in_lds != 0 && h->program_in_lds != 2) {
-        // team kernel: one instance per workgroup; as many workgroups per CU as their LDS (scratch + slice) allows
-        const size_t lds = ((size_t)CPG_TEAM_SLICE_OFF + (size_t)h->Rs.slice_doubles) * sizeof(double);
-        if (lds <= h->lds_limit) {
-            long long per_cu = (long long)(h->lds_limit / lds);
-            if (per_cu * CPG_GENT_W > 16) per_cu = 16 / CPG_GENT_W;
-            if (CPG_GENT_W <= 4 && per_cu * CPG_GENT_W > 4) per_cu = 4 / CPG_GENT_W;       // (kernels built for one wavefront per SIMD)
-            if (h->blocks_per_cu > 0 && per_cu > h->blocks_per_cu) per_cu = h->blocks_per_cu;
-            long long blocks = Bt.B;
-            if (blocks > (long long)h->num_cu * per_cu) blocks = (long long)h->num_cu * per_cu;
-            if (blocks < 1) blocks = 1;
-            int rc;
-            if ((rc = ensure(h->scratch, (size_t)blocks * (size_t)h->Rs.buf_doubles * sizeof(double)))) return rc;
-            Bt.scratch = (double *)h->scratch.p;
-            return launch_team(h, stream, S, Bt, (int)blocks, lds);
-        }
-    }
-#endif
-#ifdef CPG_GENR_HEADER
-    if (h->Rs.ok && !h->R.shared_mats && h->program_in_lds != 0 && h->program_in_lds != 2) {
-        // resident kernel: one workgroup per CU, as many wavefronts (<= 4: one per SIMD) as slices fit the LDS
-#ifdef CPG_GENR_TABLES_GLOBAL
-        const size_t tab = 0;                          // (the executor's tables stay in global memory)
-#else
-        const size_t tab = (size_t)(((CPG_GENR_NSTEPS + 3) / 4) * 256 + ((CPG_GENR_NCHUNKS + 3) / 4) * 256) * sizeof(unsigned short);
-#endif
-        const size_t slice = (size_t)h->Rs.slice_doubles * sizeof(double);
-        int NW = h->waves_per_block > 0 ? h->waves_per_block : 4;
-        if (NW > 4) NW = 4;
-        while (NW > 1 && tab + (size_t)NW * slice > h->lds_limit) NW--;
-        if (tab + (size_t)NW * slice <= h->lds_limit) {
-            long long blocks = (Bt.B + NW - 1) / NW;
-            if (blocks > (long long)h->num_cu) blocks = h->num_cu;
-            int rc;
-            if ((rc = ensure(h->scratch, (size_t)blocks * NW * (size_t)h->Rs.buf_doubles * sizeof(double)))) return rc;
-            Bt.scratch = (double *)h->scratch.p;
-            const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64;
-#define Z(a, b) if (nsx <= a && nsz <= b) return launch_resident_t<a, b>(h, stream, S, Bt, (int)blocks, NW, tab + (size_t)NW * slice);
-            CPG_KERNELS_REFACTOR(Z)
-#undef Z
-        }
-    }
-#endif
-#ifdef CPG_GENI_HEADER
-    if (h->R.gi_ok && h->program_in_lds != 0 && h->program_in_lds != 2) {
-        const int W = 8;                               // one workgroup of eight wavefronts per CU shares the tables       // generated instance executor (cpg_hip_set_program_placement(0): the streaming one)
-        const size_t tab = (size_t)(((CPG_GENI_NSTEPS + 3) / 4) * 256 + ((CPG_GENI_NCHUNKS + 3) / 4) * 256) * sizeof(unsigned short);
-        const size_t nq = (size_t)(h->F.n + h->F.m);
-        size_t per_wave = (size_t)(CPG_GENI_NSLOTS + CPG_GEN_EXTRA_SLOTS) + nq + (nq & 1);   // work vector | q | u ...
-#ifdef CPG_GENI_FAC_NSTEPS
-        const size_t fac = (size_t)h->R.nnzL + nq + 1;                                        // ... or the factor (+ a zero slot) while it is computed
-#else
-        const size_t fac = (size_t)h->R.nnzL + nq;                                            // ... or the factor while it is computed
-#endif
-        if (per_wave < fac) per_wave = fac + (fac & 1);
-        const size_t lds = tab + (size_t)W * per_wave * sizeof(double);
-        if (lds <= h->lds_limit) {
-            const int per_cu = 1;                      // 8 wavefronts per CU: the register budget of the kernel
-            long long blocks = (Bt.B + W - 1) / W;
-            const long long cap = (long long)h->num_cu * per_cu;
-            if (blocks > cap) blocks = cap;
-            int rc;
-            if ((rc = ensure(h->scratch, (size_t)blocks * W * (size_t)h->R.buf_doubles * sizeof(double)))) return rc;
-            Bt.scratch = (double *)h->scratch.p;
-            const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64;
-#define Z(a, b) if (nsx <= a && nsz <= b) return launch_instance_t<a, b>(h, stream, S, Bt, (int)blocks, W, lds);
-            CPG_KERNELS_REFACTOR(Z)
-#undef Z
-        }
-    }
-#endif
-#ifdef CPG_REFACTOR_CR_LDS
-    if (!h->R.shared_mats && h->program_in_lds != 0) {       // (cpg_hip_set_program_placement(0): entry words through L2, as before)
-        const int W8 = 8;
-        const size_t tab = (((size_t)h->R.sol_nnz + 1) / 2) * sizeof(double);
-        const size_t lds8 = tab + (size_t)W8 * h->R.sol_slots * sizeof(double);
-        if (lds8 <= h->lds_limit) {
-            long long blocks = (Bt.B + W8 - 1) / W8;
-            if (blocks > (long long)h->num_cu) blocks = h->num_cu;
-            int rc;
-            if ((rc = ensure(h->scratch, (size_t)blocks * W8 * (size_t)h->R.buf_doubles * sizeof(double)))) return rc;
-            Bt.scratch = (double *)h->scratch.p;
-            const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64;
-#define Z(a, b) if (nsx <= a && nsz <= b) return launch_refactor_crlds_t<a, b>(h, stream, S, Bt, (int)blocks, W8, lds8);
-            CPG_KERNELS_REFACTOR(Z)
-#undef Z
-        }
-    }
-#endif
-#ifdef CPG_GENS_HEADER
-    if (!h->R.shared_mats && !h->R.gs_ok) {
-        set_error("this library's per-instance substitution program was generated for a different family"); return CPG_E_BADARG; }
-    const size_t lds = (size_t)W * (size_t)(h->R.shared_mats ? h->R.sol_slots : h->R.sol_slots + CPG_GEN_EXTRA_SLOTS) * sizeof(double);
-#else
-    const size_t lds = (size_t)W * h->R.sol_slots * sizeof(double);
-#endif
-    if (lds > h->lds_limit) { set_error("work vectors do not fit the LDS"); return CPG_E_UNSUPPORTED; }
-    int per_cu = h->blocks_per_cu > 0 ? h->blocks_per_cu : CPG_REFACTOR_WAVES_PER_SIMD;    // workgroups of 4 waves
-    if (per_cu > CPG_REFACTOR_WAVES_PER_SIMD) per_cu = CPG_REFACTOR_WAVES_PER_SIMD;
-    if ((long long)per_cu * (long long)lds > (long long)h->lds_limit) per_cu = (int)(h->lds_limit / lds);
-    long long blocks = (Bt.B + W - 1) / W;
-    const long long cap = (long long)h->num_cu * per_cu;
-    if (blocks > cap) blocks = cap;
-    int rc;
-    if ((rc = ensure(h->scratch, (size_t)blocks * W * (size_t)h->R.buf_doubles * sizeof(double)))) return rc;
-    Bt.scratch = (double *)h->scratch.p;
-    return launch_refactor(h, stream, S, Bt, (int)blocks, W, lds);
+static int np_var(cpg_handle_t h) { return h->conic ? h->C.np_var : h->refactor_mode ? h->R.np_var : h->U.np_var; }
+// the checks every solve entry point makes: the handle, its update tables, B >= 0, the result buffers, theta when the family has parameters
+static int check_solve_args(cpg_handle_t h, int64_t B, const double *theta, const double *prim, const double *dual, const double *obj,
+                            const int32_t *iter, const int32_t *status, const double *pri_res, const double *dua_res) {
+    if (!h) { set_error("null handle"); return CPG_E_BADARG; }
+    if (!h->have_update) { set_error("cpg_hip_set_update has not been called"); return CPG_E_BADARG; }
+    if (B < 0 || !prim || !dual || !obj || !iter || !status || !pri_res || !dua_res || (np_var(h) > 0 && !theta)) {
+        set_error("null buffer"); return CPG_E_BADARG; }
+    return CPG_OK;
 }
 
 int cpg_hip_solve_batch_device_state(cpg_handle_t h, int64_t B, const double *d_theta, const double *d_state_in,
                                      double *d_state_out, double *d_prim, double *d_dual, double *d_obj,
                                      int32_t *d_iter, int32_t *d_status, double *d_pri, double *d_dua) {
-    if (!h) { set_error("null handle"); return CPG_E_BADARG; }
-    if (h->conic && (d_state_in || d_state_out)) {
+    if (h && h->conic && (d_state_in || d_state_out)) {
         // the reference builds a new Clarabel solver per solve (solvers/clarabel.py:201-204): nothing carries over
         set_error("a conic (interior-point) handle has no state between solves"); return CPG_E_BADARG; }
-    if (!h->have_update) { set_error("cpg_hip_set_update has not been called"); return CPG_E_BADARG; }
-    if (B < 0 || !d_prim || !d_dual || !d_obj || !d_iter || !d_status || !d_pri || !d_dua || ((h->conic ? h->C.np_var : h->refactor_mode ? h->R.np_var : h->U.np_var) > 0 && !d_theta)) {
-        set_error("null buffer"); return CPG_E_BADARG; }
-    if (B == 0) return CPG_OK;
-    int rc = rt_set_device(h->device);
-    if (rc) return rc;
-    if (h->conic) {
-        const size_t per_wave = (size_t)h->C.lds_doubles * sizeof(double);
-        // the kernel is compiled for CPG_CONIC_WAVES_PER_SIMD waves per SIMD (register budget).  The
-        // family's index tables get a block-shared LDS copy whenever a workgroup still fits; measured
-        // best on MI355X (ADP): workgroups of 8 waves (15.8 ms; 17.3 with 7, 19.4 with 6).
-        int W = h->waves_per_block > 0 ? (h->waves_per_block > 8 ? 8 : h->waves_per_block) : 8;
-        const size_t tab = (size_t)h->C.tab_doubles * sizeof(double);
-        const bool tables_in_lds = h->program_in_lds != 0 && tab + per_wave <= h->lds_limit;
-        const size_t fixed = tables_in_lds ? tab : 0;
-        while (W > 1 && fixed + (size_t)W * per_wave > h->lds_limit) W--;
-        if (h->waves_per_block <= 0) {
-            // what counts is the number of resident waves per CU (the kernel is VALU-issue bound from ~12 on): when a
-            // second 8-wave workgroup just misses the LDS, two smaller ones beat one (ADP with the previous-iterate
-            // copy: 8 + 0 waves at 83.8 KB per workgroup, 7 + 7 at 75.1 KB)
-            int best = W, best_res = 0;
-            for (int w2 = W; w2 >= 4; w2--) {
-                int pc = (int)(h->lds_limit / (fixed + (size_t)w2 * per_wave));
-                if (h->blocks_per_cu > 0 && pc > h->blocks_per_cu) pc = h->blocks_per_cu;
-                int res = pc * w2; if (res > 4 * CPG_CONIC_WAVES_PER_SIMD) res = 4 * CPG_CONIC_WAVES_PER_SIMD;
-                if (res > best_res) { best_res = res; best = w2; }
-            }
-            W = best;
-        }
-        // (+ 16 doubles behind the last wavefront's slice: the specialised kernel's per-cone loops are unrolled to the family's largest
-        // cone and load past the end of a shorter trailing cone before they mask the use -- inside the allocation with this pad)
-        const size_t lds = fixed + (size_t)W * per_wave + (fixed + (size_t)W * per_wave + 128 <= h->lds_limit ? 128 : 0);
-        long long blocks = (B + W - 1) / W;
-        int per_cu = (int)(h->lds_limit / lds); if (per_cu < 1) per_cu = 1;
-        if (h->blocks_per_cu > 0 && per_cu > h->blocks_per_cu) per_cu = h->blocks_per_cu;
-        if (per_cu * W > 4 * CPG_CONIC_WAVES_PER_SIMD) per_cu = (4 * CPG_CONIC_WAVES_PER_SIMD) / W;
-        if (per_cu < 1) per_cu = 1;
-        const long long cap = (long long)h->num_cu * per_cu;
-        if (blocks > cap) blocks = cap;
-        cpg::DevBatch Bt = make_batch(B, d_theta, nullptr, nullptr, d_prim, d_dual, d_obj, d_iter, d_status, d_pri, d_dua);
-        Bt.counter = h->d_counter;
-        RT_CHECK(hipMemsetAsync(h->d_counter, 0, sizeof(unsigned), h->stream));
-        RT_CHECK(hipEventRecord(h->ev0, h->stream));
-        rc = launch_conic(h, Bt, (int)blocks, W, lds, tables_in_lds);
-        if (rc) return rc;
-        RT_CHECK(hipEventRecord(h->ev1, h->stream));
-        return CPG_OK;
-    }
-    if (h->refactor_mode) {
-        cpg::DevBatch Bt = make_batch(B, d_theta, d_state_in, d_state_out, d_prim, d_dual, d_obj, d_iter, d_status, d_pri, d_dua);
-        Bt.counter = h->d_counter;
-        RT_CHECK(hipMemsetAsync(h->d_counter, 0, 4 * sizeof(unsigned), h->stream));
-        RT_CHECK(hipEventRecord(h->ev0, h->stream));
-        rc = launch_per_instance(h, h->stream, h->S, Bt);
-        if (rc) return rc;
-        RT_CHECK(hipEventRecord(h->ev1, h->stream));
-        h->two_phase_last = false;
-        return CPG_OK;
-    }
-    // rho adaptation on the shared factor: hybrid execution when a per-instance factor handle is linked
-    // (cpg_hip_set_handover); without one the kernel flags the instances whose rho changes (status -2) and the
-    // host layer re-solves them through the per-instance factor path
-    const bool two_phase = h->S.adaptive_rho && h->S.adaptive_rho_interval > 0 && h->linked != nullptr;
-    if (h->S.adaptive_rho && h->S.adaptive_rho_interval > 0 && h->linked == nullptr && !h->flag_rho_changes) {
-        // a shared factor cannot follow a rho change: without a linked per-instance factor handle every instance whose rho
-        // estimate leaves the tolerance band would come back UNSOLVED under the internal status -2 -- refuse instead
-        set_error("rho adaptation is on and this shared-factor handle has no per-instance factor handle linked (cpg_hip_set_handover): "
-                  "link one, or turn it off (cpg_hip_set_build_option(h, \"adaptive_rho\", 0)), or accept instances flagged "
-                  "CPG_STATUS_NEEDS_REFACTOR (-2) with cpg_hip_set_build_option(h, \"flag_rho_changes\", 1)");
-        return CPG_E_UNSUPPORTED;
-    }
-    if (two_phase && !h->linked->refactor_mode) { set_error("linked handle has no per-instance factor tables (cpg_hip_set_refactor)"); return CPG_E_BADARG; }
-    const int G = h->inst_per_wave;
-    const size_t N = (size_t)(h->F.n + h->F.m);
-#ifdef CPG_GENQ_HEADER
-    if (h->squad_ok && G == 1 && h->program_in_lds == 3) {
-        // squad executor (on request: it lost the A/B against the LDS-resident program on MI355X, HISTORY.md round 6): CPG_GENQ_W
-        // instances per workgroup of CPG_GENQ_W wavefronts, the program in their registers
-        const size_t lds_q = cpg::squad_lds_bytes((unsigned)h->F.n, (unsigned)h->F.m);
-        if (lds_q <= h->lds_limit) {
-            int per_cu = (int)(h->lds_limit / lds_q);
-            const int by_regs = 8 / CPG_GENQ_W > 0 ? 8 / CPG_GENQ_W : 1;     // two wavefronts per SIMD
-            if (per_cu > by_regs) per_cu = by_regs;
-            if (h->blocks_per_cu > 0 && per_cu > h->blocks_per_cu) per_cu = h->blocks_per_cu;
-            long long blocks = (B + CPG_GENQ_W - 1) / CPG_GENQ_W;
-            const long long cap = (long long)h->num_cu * per_cu;
-            if (blocks > cap) blocks = cap;
-            cpg::DevBatch Bt = make_batch(B, d_theta, d_state_in, d_state_out, d_prim, d_dual, d_obj, d_iter, d_status, d_pri, d_dua);
-            Bt.counter = h->d_counter;
-            const size_t state_bytes = (size_t)B * ((size_t)h->F.n + 2 * (size_t)h->F.m + 1) * sizeof(double);
-            if (two_phase) {
-                if (!d_state_out) { if ((rc = ensure(h->ho_state, state_bytes))) return rc; }
-                if ((rc = ensure(h->ho_list, (size_t)B * sizeof(int)))) return rc;
-                Bt.ho_state = d_state_out ? d_state_out : (double *)h->ho_state.p;
-                Bt.ho_list = (int *)h->ho_list.p; Bt.ho_count = h->d_counter + 1;
-            }
-            RT_CHECK(hipMemsetAsync(h->d_counter, 0, 4 * sizeof(unsigned), h->stream));
-            RT_CHECK(hipEventRecord(h->ev0, h->stream));
-            rc = launch_squad(h, Bt, (int)blocks, lds_q);
-            if (rc) return rc;
-            h->two_phase_last = two_phase;
-            if (two_phase) {
-                RT_CHECK(hipEventRecord(h->ev_mid, h->stream));
-                cpg::DevBatch B2 = make_batch(B, d_theta, Bt.ho_state, d_state_out, d_prim, d_dual, d_obj, d_iter, d_status, d_pri, d_dua);
-                B2.counter = h->d_counter + 2; B2.list = Bt.ho_list; B2.list_count = h->d_counter + 1; B2.resume = 1;
-                rc = launch_per_instance(h->linked, h->stream, h->S, B2);
-                if (rc) return rc;
-            }
-            RT_CHECK(hipEventRecord(h->ev1, h->stream));
-            return CPG_OK;
-        }
-        if (h->program_in_lds == 3) { set_error("the squad executor's LDS need exceeds the device limit"); return CPG_E_UNSUPPORTED; }
-    }
-#endif
-    if (h->program_in_lds == 3) { set_error("this library carries no squad executor for the family (cpg_hip_set_program_placement(3))"); return CPG_E_UNSUPPORTED; }
-#if defined(CPG_GEN_HEADER) && defined(CPG_GEN_N)
-    const size_t per_wave = (size_t)G * (h->F.n_slots + CPG_GEN_EXTRA_SLOTS) * sizeof(double);
-#else
-    const size_t per_wave = (size_t)G * h->F.n_slots * sizeof(double);
-#endif
-    // LDS-resident program: one workgroup per CU, as many waves as fit next to the program
-    const cpg::DevRagged &R = h->F.kkt_ragged;
-#ifdef CPG_GEN_HEADER
-    const size_t tab_doubles = (size_t)((R.n_chunks + 3) & ~3) * 16;     // 16-bit output-slot table, four chunks per entry group
-#else
-    const size_t tab_doubles = (size_t)R.n_chunks * 34;     // desc (u32 x 64) + ctab (int x 4)
-#endif
-#ifdef CPG_GEN_HEADER
-    const size_t nnzp = (size_t)R.nnz + CPG_GEN_PAD;
-#else
-    const size_t nnzp = (size_t)R.nnz;
-#endif
-#ifdef CPG_GEN_COMPRESSED
-    const size_t prog_bytes = R.n_chunks > 0 ? ((size_t)R.n_dict + (nnzp + 1) / 2 + tab_doubles) * 8 : 0;
-#else
-#ifdef CPG_GEN_PADDED_OFFSETS
-    const size_t n_off = (size_t)64 * ((CPG_GEN_PADDED_OFFSETS + 3) & ~3);    // operand offsets of all 64 lanes of every step
-#else
-    const size_t n_off = nnzp;
-#endif
-    const size_t prog_bytes = R.n_chunks > 0 ? (nnzp + (n_off + 3) / 4 + tab_doubles) * 8 : 0;
-#endif
-    bool in_lds = false;
-    int W = h->waves_per_block;
-    // table-driven kernels, automatic placement: the streaming executor (program through L2, operands
-    // of eight steps in flight, more resident waves) beats the LDS-resident table walk -- 1.44 M vs
-    // 1.10 M instances/s on MPC 12/4/10; the LDS-resident form remains for G = 2 and on request
-    const int placement = h->program_in_lds == 2 ? -1 : h->program_in_lds;     // (2 concerns per-instance factor handles only)
-#ifdef CPG_GEN_HEADER
-    const bool prefer_stream = false;   // family library: the generated executor works on the LDS-resident program
-#else
-    const bool prefer_stream = placement == -1 && G == 1 && h->F.kkt_stream.n_pairs > 0;
-#endif
-    if (placement != 0 && R.n_chunks > 0 && !prefer_stream) {
-        const size_t fixed = N * 8 + prog_bytes;
-        int wfit = fixed < h->lds_limit ? (int)((h->lds_limit - fixed) / per_wave) : 0;
-        // every slot class has an LDS kernel for <= 8 waves (<= 4 for G = 2 on the larger classes);
-        // more waves only on explicit request (cpg_hip_set_launch) where such a kernel exists
-        int wcap = h->waves_per_block > 0 ? 16 : (G == 2 ? 4 : 8);
-#ifdef CPG_GEN_HEADER
-        if (h->waves_per_block <= 0) {   // family library: as many waves as its widest compiled kernel admits
-            const int nsx_ = (h->F.n + 63) / 64, nsz_ = (h->F.m + 63) / 64;
-#define Y(a, b, v, g, wm) if (nsx_ <= a && nsz_ <= b && G == g && wm > wcap) wcap = wm;
-            CPG_KERNELS_LDS(Y)
-#undef Y
-        }
-#endif
-        if (wfit > wcap) wfit = wcap;
-        if (wfit >= 4 || (placement == 1 && wfit >= 1)) {
-            in_lds = true;
-            if (W <= 0 || W > wfit) W = wfit;
-        } else if (placement == 1) {
-            set_error("solve program does not fit into LDS next to the work vectors"); return CPG_E_UNSUPPORTED;
-        }
-    }
-    if (!in_lds && (W <= 0 || W > 4)) W = 4;
-    const size_t lds = N * 8 + (in_lds ? prog_bytes : 0) + (size_t)W * per_wave;
-    if (lds > h->lds_limit) { set_error("work vectors do not fit the 160 KiB LDS; lower waves_per_block / inst_per_wave"); return CPG_E_UNSUPPORTED; }
-    const long long ngroups = (B + G - 1) / G;
-    int per_cu = h->blocks_per_cu;
-    if (in_lds) per_cu = 1;
-    else if (per_cu <= 0) {   // as many blocks as LDS and the register budget (CPG_MIN_WAVES_PER_SIMD) admit
-        per_cu = (int)(h->lds_limit / (lds ? lds : 1));
-        const int by_regs = (CPG_MIN_WAVES_PER_SIMD * 4) / W;
-        if (per_cu > by_regs) per_cu = by_regs;
-        if (per_cu < 1) per_cu = 1;
-    }
-    long long blocks = (ngroups + W - 1) / W;
-    const long long cap = (long long)h->num_cu * per_cu;
-    if (blocks > cap) blocks = cap;
+    int rc = check_solve_args(h, B, d_theta, d_prim, d_dual, d_obj, d_iter, d_status, d_pri, d_dua);
+    if (rc || B == 0) return rc;
+    if ((rc = rt_set_device(h->device))) return rc;
     cpg::DevBatch Bt = make_batch(B, d_theta, d_state_in, d_state_out, d_prim, d_dual, d_obj, d_iter, d_status, d_pri, d_dua);
     Bt.counter = h->d_counter;
-    const size_t state_bytes = (size_t)B * ((size_t)h->F.n + 2 * (size_t)h->F.m + 1) * sizeof(double);
-    if (two_phase) {
-        // hand-over buffers: the workspace of every instance whose rho changes (the caller's state_out rows serve
-        // when it gave a buffer: the continuing kernel overwrites them with the final workspace) and their numbers
-        if (!d_state_out) { if ((rc = ensure(h->ho_state, state_bytes))) return rc; }
-        if ((rc = ensure(h->ho_list, (size_t)B * sizeof(int)))) return rc;
-        Bt.ho_state = d_state_out ? d_state_out : (double *)h->ho_state.p;
-        Bt.ho_list = (int *)h->ho_list.p; Bt.ho_count = h->d_counter + 1;
-    }
-    RT_CHECK(hipMemsetAsync(h->d_counter, 0, 4 * sizeof(unsigned), h->stream));
-    RT_CHECK(hipEventRecord(h->ev0, h->stream));
-    rc = launch(h, Bt, (int)blocks, W, G, lds, in_lds);
-    if (rc) return rc;
-    h->two_phase_last = two_phase;
-    if (two_phase) {
-        RT_CHECK(hipEventRecord(h->ev_mid, h->stream));
-        cpg::DevBatch B2 = make_batch(B, d_theta, Bt.ho_state, d_state_out, d_prim, d_dual, d_obj, d_iter, d_status, d_pri, d_dua);
-        B2.counter = h->d_counter + 2; B2.list = Bt.ho_list; B2.list_count = h->d_counter + 1; B2.resume = 1;
-        rc = launch_per_instance(h->linked, h->stream, h->S, B2);
-        if (rc) return rc;
-    }
-    RT_CHECK(hipEventRecord(h->ev1, h->stream));
-    return CPG_OK;
+    if (h->conic) return solve_conic(h, Bt);
+    return h->refactor_mode ? solve_per_instance(h, Bt) : solve_shared(h, Bt);
 }
 
 int cpg_hip_solve_batch_device(cpg_handle_t h, int64_t B, const double *d_theta, double *d_prim, double *d_dual,
@@ -2453,53 +2415,35 @@ int cpg_hip_solve_batch(cpg_handle_t h, int64_t B, const double *theta, double *
 int cpg_hip_solve_batch_state(cpg_handle_t h, int64_t B, const double *theta, const double *state_in, double *state_out,
                               double *prim, double *dual, double *obj, int32_t *iter, int32_t *status,
                               double *pri_res, double *dua_res) {
-    if (!h) { set_error("null handle"); return CPG_E_BADARG; }
-    if (!h->have_update) { set_error("cpg_hip_set_update has not been called"); return CPG_E_BADARG; }
-    if (B < 0 || !prim || !dual || !obj || !iter || !status || !pri_res || !dua_res || ((h->conic ? h->C.np_var : h->refactor_mode ? h->R.np_var : h->U.np_var) > 0 && !theta)) {
-        set_error("null buffer"); return CPG_E_BADARG; }
-    if (B == 0) return CPG_OK;
-    int rc = rt_set_device(h->device);
-    if (rc) return rc;
-    const size_t b = (size_t)B;
-    const size_t npv = (size_t)(h->conic ? h->C.np_var : h->refactor_mode ? h->R.np_var : h->U.np_var);
-    if ((rc = ensure(h->s_theta, b * npv * sizeof(double)))) return rc;
-    if ((rc = ensure(h->s_prim, b * h->F.n_prim * sizeof(double)))) return rc;
-    if ((rc = ensure(h->s_dual, b * h->F.n_dual * sizeof(double)))) return rc;
-    if ((rc = ensure(h->s_obj, b * sizeof(double)))) return rc;
-    if ((rc = ensure(h->s_pri, b * sizeof(double)))) return rc;
-    if ((rc = ensure(h->s_dua, b * sizeof(double)))) return rc;
-    if ((rc = ensure(h->s_iter, b * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(h->s_status, b * sizeof(int32_t)))) return rc;
+    int rc = check_solve_args(h, B, theta, prim, dual, obj, iter, status, pri_res, dua_res);
+    if (rc || B == 0) return rc;
+    if ((rc = rt_set_device(h->device))) return rc;
+    const size_t b = (size_t)B, npv = (size_t)np_var(h);
+    ResultBufs &out = h->s_out;
+    if ((rc = ensure(h->s_theta, b * npv * sizeof(double))) || (rc = out.ensure(b, h->F))) return rc;
     if ((rc = rt_h2d(h, h->s_theta.p, theta, b * npv * sizeof(double)))) return rc;
     const size_t state_bytes = b * ((size_t)h->F.n + 2 * (size_t)h->F.m + 1) * sizeof(double);
     if (state_in) { if ((rc = ensure(h->s_state_in, state_bytes))) return rc; if ((rc = rt_h2d(h, h->s_state_in.p, state_in, state_bytes))) return rc; }
     if (state_out) { if ((rc = ensure(h->s_state_out, state_bytes))) return rc; }
     rc = cpg_hip_solve_batch_device_state(h, B, (const double *)h->s_theta.p, state_in ? (const double *)h->s_state_in.p : nullptr,
-                                          state_out ? (double *)h->s_state_out.p : nullptr, (double *)h->s_prim.p,
-                                          (double *)h->s_dual.p, (double *)h->s_obj.p, (int32_t *)h->s_iter.p,
-                                          (int32_t *)h->s_status.p, (double *)h->s_pri.p, (double *)h->s_dua.p);
+                                          state_out ? (double *)h->s_state_out.p : nullptr, (double *)out.prim.p, (double *)out.dual.p,
+                                          (double *)out.obj.p, (int32_t *)out.iter.p, (int32_t *)out.status.p,
+                                          (double *)out.pri.p, (double *)out.dua.p);
     if (rc) return rc;
     if (state_out) { if ((rc = rt_d2h(h, state_out, h->s_state_out.p, state_bytes))) return rc; }
-    if ((rc = rt_d2h(h, prim, h->s_prim.p, b * h->F.n_prim * sizeof(double)))) return rc;
-    if ((rc = rt_d2h(h, dual, h->s_dual.p, b * h->F.n_dual * sizeof(double)))) return rc;
-    if ((rc = rt_d2h(h, obj, h->s_obj.p, b * sizeof(double)))) return rc;
-    if ((rc = rt_d2h(h, pri_res, h->s_pri.p, b * sizeof(double)))) return rc;
-    if ((rc = rt_d2h(h, dua_res, h->s_dua.p, b * sizeof(double)))) return rc;
-    if ((rc = rt_d2h(h, iter, h->s_iter.p, b * sizeof(int32_t)))) return rc;
-    if ((rc = rt_d2h(h, status, h->s_status.p, b * sizeof(int32_t)))) return rc;
+    if ((rc = out.copy_out(h->stream, 0, b, h->F, prim, dual, obj, pri_res, dua_res, iter, status))) return rc;
     return rt_sync(h);
 }
 
 // ---- streaming many batches from host memory: transfers hidden behind the solve kernel ----------------
 // Two sets of device buffers; batch i is copied in on `copy_in` while batch i - 1 is being solved on the
 // handle's stream and batch i - 2 is copied out on `copy_out`; events chain the three stages.
-struct PipeSet { DevBuf theta, prim, dual, obj, pri, dua, iter, status; hipEvent_t in_done{}, k_done{}, out_done{}; };
+struct PipeSet { DevBuf theta; ResultBufs out; hipEvent_t in_done{}, k_done{}, out_done{}; };
 struct cpg_pipe_s { hipStream_t copy_in{}, copy_out{}; PipeSet set[2]; bool ready = false; };
 static void free_pipe(cpg_pipe_s *p) {
     if (!p) return;
     for (auto &s : p->set) {
-        free_buf(s.theta); free_buf(s.prim); free_buf(s.dual); free_buf(s.obj); free_buf(s.pri); free_buf(s.dua);
-        free_buf(s.iter); free_buf(s.status);
+        free_buf(s.theta); s.out.free();
         if (p->ready) { hipEventDestroy(s.in_done); hipEventDestroy(s.k_done); hipEventDestroy(s.out_done); }
     }
     if (p->ready) { hipStreamDestroy(p->copy_in); hipStreamDestroy(p->copy_out); }
@@ -2509,14 +2453,10 @@ static void free_pipe(cpg_pipe_s *p) {
 int cpg_hip_solve_batches_pipelined(cpg_handle_t h, int64_t B, int32_t n_batches, const double *theta, double *prim,
                                     double *dual, double *obj, int32_t *iter, int32_t *status, double *pri_res,
                                     double *dua_res) {
-    if (!h) { set_error("null handle"); return CPG_E_BADARG; }
-    if (!h->have_update) { set_error("cpg_hip_set_update has not been called"); return CPG_E_BADARG; }
-    const size_t npv = (size_t)(h->conic ? h->C.np_var : h->refactor_mode ? h->R.np_var : h->U.np_var);
-    if (B < 0 || n_batches < 0 || !prim || !dual || !obj || !iter || !status || !pri_res || !dua_res || (npv > 0 && !theta)) {
-        set_error("null buffer"); return CPG_E_BADARG; }
-    if (B == 0 || n_batches == 0) return CPG_OK;
-    int rc = rt_set_device(h->device);
-    if (rc) return rc;
+    // (a negative batch count is refused like a negative B)
+    int rc = check_solve_args(h, n_batches < 0 ? -1 : B, theta, prim, dual, obj, iter, status, pri_res, dua_res);
+    if (rc || B == 0 || n_batches == 0) return rc;
+    if ((rc = rt_set_device(h->device))) return rc;
     if (!h->pipe) {
         // built aside and published only when every stream / event exists: a failed create must not leave a
         // half-initialised pipe behind for the next call
@@ -2541,12 +2481,9 @@ int cpg_hip_solve_batches_pipelined(cpg_handle_t h, int64_t B, int32_t n_batches
         h->pipe = np_;
     }
     cpg_pipe_s &P = *h->pipe;
-    const size_t b = (size_t)B, np_ = (size_t)h->F.n_prim, nd = (size_t)h->F.n_dual;
-    for (auto &s : P.set) {
-        if ((rc = ensure(s.theta, b * npv * 8)) || (rc = ensure(s.prim, b * np_ * 8)) || (rc = ensure(s.dual, b * nd * 8)) ||
-            (rc = ensure(s.obj, b * 8)) || (rc = ensure(s.pri, b * 8)) || (rc = ensure(s.dua, b * 8)) ||
-            (rc = ensure(s.iter, b * 4)) || (rc = ensure(s.status, b * 4))) return rc;
-    }
+    const size_t b = (size_t)B, npv = (size_t)np_var(h);
+    for (auto &s : P.set)
+        if ((rc = ensure(s.theta, b * npv * sizeof(double))) || (rc = s.out.ensure(b, h->F))) return rc;
     for (int i = 0; i < n_batches; i++) {
         PipeSet &s = P.set[i & 1];
         const size_t o = (size_t)i * b;
@@ -2554,22 +2491,16 @@ int cpg_hip_solve_batches_pipelined(cpg_handle_t h, int64_t B, int32_t n_batches
         if (npv) RT_CHECK(hipMemcpyAsync(s.theta.p, theta + o * npv, b * npv * 8, hipMemcpyHostToDevice, P.copy_in));
         RT_CHECK(hipEventRecord(s.in_done, P.copy_in));
         RT_CHECK(hipStreamWaitEvent(h->stream, s.in_done, 0));
-        rc = cpg_hip_solve_batch_device_state(h, B, (const double *)s.theta.p, nullptr, nullptr, (double *)s.prim.p, (double *)s.dual.p,
-                                              (double *)s.obj.p, (int32_t *)s.iter.p, (int32_t *)s.status.p, (double *)s.pri.p,
-                                              (double *)s.dua.p);
+        rc = cpg_hip_solve_batch_device_state(h, B, (const double *)s.theta.p, nullptr, nullptr, (double *)s.out.prim.p,
+                                              (double *)s.out.dual.p, (double *)s.out.obj.p, (int32_t *)s.out.iter.p,
+                                              (int32_t *)s.out.status.p, (double *)s.out.pri.p, (double *)s.out.dua.p);
         if (rc) {   // batches already queued copy into the caller's buffers: let them finish before handing the error back
             hipStreamSynchronize(P.copy_in); hipStreamSynchronize(h->stream); hipStreamSynchronize(P.copy_out);
             return rc;
         }
         RT_CHECK(hipEventRecord(s.k_done, h->stream));
         RT_CHECK(hipStreamWaitEvent(P.copy_out, s.k_done, 0));
-        RT_CHECK(hipMemcpyAsync(prim + o * np_, s.prim.p, b * np_ * 8, hipMemcpyDeviceToHost, P.copy_out));
-        RT_CHECK(hipMemcpyAsync(dual + o * nd, s.dual.p, b * nd * 8, hipMemcpyDeviceToHost, P.copy_out));
-        RT_CHECK(hipMemcpyAsync(obj + o, s.obj.p, b * 8, hipMemcpyDeviceToHost, P.copy_out));
-        RT_CHECK(hipMemcpyAsync(pri_res + o, s.pri.p, b * 8, hipMemcpyDeviceToHost, P.copy_out));
-        RT_CHECK(hipMemcpyAsync(dua_res + o, s.dua.p, b * 8, hipMemcpyDeviceToHost, P.copy_out));
-        RT_CHECK(hipMemcpyAsync(iter + o, s.iter.p, b * 4, hipMemcpyDeviceToHost, P.copy_out));
-        RT_CHECK(hipMemcpyAsync(status + o, s.status.p, b * 4, hipMemcpyDeviceToHost, P.copy_out));
+        if ((rc = s.out.copy_out(P.copy_out, o, b, h->F, prim, dual, obj, pri_res, dua_res, iter, status))) return rc;
         RT_CHECK(hipEventRecord(s.out_done, P.copy_out));
     }
     RT_CHECK(hipStreamSynchronize(P.copy_out));
