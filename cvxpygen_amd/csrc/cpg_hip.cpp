@@ -557,7 +557,7 @@ static int launch_per_instance(cpg_handle_t h, rt_stream_t stream, const cpg::De
         const size_t nq = (size_t)(h->F.n + h->F.m);
         size_t per_wave = (size_t)(CPG_GENI_NSLOTS + CPG_GEN_EXTRA_SLOTS) + nq + (nq & 1);   // work vector | q | u ...
 #ifdef CPG_GENI_FAC_NSTEPS
-        const size_t fac = (size_t)h->R.nnzL + nq + 1;                                        // ... or the factor (+ a zero slot) while it is computed
+        const size_t fac = (size_t)CPG_GENI_FAC_ZERO + 1;                                     // ... or the factor (+ a zero slot) while it is computed
 #else
         const size_t fac = (size_t)h->R.nnzL + nq;                                            // ... or the factor while it is computed
 #endif
@@ -1518,6 +1518,179 @@ int cpg_hip_set_update(cpg_handle_t h, const cpg_osqp_update_t *u) {
     return CPG_OK;
 }
 
+// KKT value of every destination of shared-matrix mode's factorisation (L entries, then the n + m pivots): a constant of
+// the family (fkc; sigma included on the pivots), except the -1 / rho_vec of the (2,2) diagonal (fkrow: its row, else -1)
+static bool kkt_constants(cpg_handle_t h, const cpg_osqp_refactor_t *r, std::vector<double> &fkc, std::vector<int> &fkrow) {
+    const size_t m = h->F.m, nd = (size_t)r->nnzL + h->F.n + m;
+    fkc.assign(nd, 0.0); fkrow.assign(nd, -1);
+    for (size_t d = 0; d < nd; d++) {
+        const int kind = r->ksrc_kind[d], idx = r->ksrc_idx[d];
+        const bool piv = d >= (size_t)r->nnzL;
+        if (kind == CPG_K_P) { if (idx < 0 || idx >= r->nnzP) return false; fkc[d] = r->Ps[idx] + (piv ? h->F.sigma : 0.0); }
+        else if (kind == CPG_K_A) { if (idx < 0 || idx >= r->nnzA) return false; fkc[d] = r->As[idx]; }
+        else if (kind == CPG_K_SIGMA) fkc[d] = h->F.sigma;
+        else if (kind == CPG_K_RHO) { if (idx < 0 || (size_t)idx >= m) return false; fkrow[d] = idx; }
+        else if (kind != CPG_K_NONE) return false;
+    }
+    return true;
+}
+
+#ifdef CPG_GENI_HEADER
+// What the generated instance executor of shared-matrix mode runs: the plain plan of cpg_osqp_refactor_t (nnzX 0: operand
+// positions of the schedule relative -- a, b entries of L, k a column of 1 / d --, destinations without a flag, value sources
+// 0 - 3) or a merged one (the f_* / sol_* of a cpg_osqp_resident_t: positions absolute in [M | 1/d | X | 1.0 | 0.0], bit 31
+// of a destination marks a pivot, value source 4 = X[idx]).
+struct InstanceTables {
+    int nnzX;
+    int sol_chunks, sol_nnz, sol_slots;
+    const int32_t *sol_ctab; const uint32_t *sol_desc; const uint16_t *sol_cols; const int32_t *sol_kind, *sol_idx;
+    int fac_chunks, fac_triples;
+    const int32_t *fac_ctab; const uint32_t *fac_task, *fac_len, *fac_a, *fac_b, *fac_k;
+};
+
+// The executor's tables of g -- when g is what this library's cpg_instance_<name>.h was generated from: R.gi_ok; otherwise
+// R.gi_ok stays 0 and the handle streams.  fkc / fkrow: kkt_constants.
+static int set_instance_executor(cpg_handle_t h, const cpg_osqp_refactor_t *r, const InstanceTables &g,
+                                 const std::vector<double> &fkc, const std::vector<int> &fkrow) {
+    std::vector<void *> &own = h->refactor_owned;
+    cpg::DevRefactor &R = h->R;
+    const size_t n = h->F.n, m = h->F.m, N = n + m;
+    int rc = CPG_OK;
+    R.gi_ok = 0;
+    std::vector<unsigned short> gcols, grows, glcol;
+    std::vector<unsigned> gsrc, gdk;
+    std::vector<unsigned long long> gtri;
+    std::vector<double> gkc;
+#ifdef CPG_GENI_N
+    const bool geni_dims = h->F.n == CPG_GENI_N && h->F.m == CPG_GENI_M && h->F.n_eq == CPG_GENI_NEQ;
+#else
+    const bool geni_dims = true;
+#endif
+#ifdef CPG_GENI_NNZX
+    const bool merged_lib = true;
+#else
+    const bool merged_lib = false;
+#endif
+    if (!(geni_dims && (g.nnzX > 0) == merged_lib && g.sol_chunks == CPG_GENI_NCHUNKS && g.sol_nnz == CPG_GENI_NNZ && g.sol_slots == CPG_GENI_NSLOTS))
+        return CPG_OK;
+    const size_t nd = (size_t)r->nnzL + N, nx = (size_t)g.nnzX;
+    const unsigned hsh = program_fingerprint(g.sol_ctab, g.sol_desc, g.sol_cols, g.sol_chunks, g.sol_nnz);
+    static const int steps[][4] = CPG_GENI_STEPS;             // {first entry, active lanes, coefficient register, lane shift} in execution order
+    static const int chunk_shift[] = CPG_GENI_CHUNK_SHIFT;
+    bool ok = hsh == CPG_GENI_FINGERPRINT;
+    {   // the row programs of the termination test carry their chunk tables as literals
+        const int nn[3] = {CPG_GENI_AROWS_N, CPG_GENI_PROWS_N, CPG_GENI_ATROWS_N};
+        for (int k = 0; ok && k < 3; k++) {
+            if ((int)h->rows_hdr[k].size() != 4 * nn[k]) ok = false;
+            for (int c2 = 0; ok && c2 < nn[k]; c2++)
+                if (h->rows_hdr[k][4 * c2] != cpg::GeniRows::len(k, c2) || h->rows_hdr[k][4 * c2 + 3] != cpg::GeniRows::off(k, c2)) ok = false;
+        }
+    }
+    if (ok) ok = generated_tables(g.sol_ctab, g.sol_desc, g.sol_cols, g.sol_chunks, g.sol_nnz, g.sol_slots, steps, CPG_GENI_NSTEPS, gcols, grows, chunk_shift);
+    if (ok) {
+        // coefficient sources per (register, lane): the steps that share a register occupy disjoint lane ranges
+        gsrc.assign((size_t)CPG_GENI_NREGS * 64, 0u);
+        glcol.assign((size_t)CPG_GENI_NREGS * 64, (unsigned short)0);
+        std::vector<char> taken((size_t)CPG_GENI_NREGS * 64, 0);
+        for (int t = 0; ok && t < CPG_GENI_NSTEPS; t++) {
+            const int e = steps[t][0], cnt = steps[t][1], reg = steps[t][2], sh = steps[t][3];
+            if (reg < 0 || reg >= CPG_GENI_NREGS) { ok = false; break; }
+            for (int l = 0; l < cnt; l++) {
+                int kind = g.sol_kind[e + l], idx = g.sol_idx[e + l];
+                if (kind == 4) {                                  // X[idx]: behind the N reciprocal pivots, read as a kind-3 source
+                    if (idx < 0 || (size_t)idx >= nx) { ok = false; break; }
+                    kind = 3; idx += (int)N;
+                }
+                if (kind < 0 || kind > 3 || idx < 0 || idx >= (1 << 28)) { ok = false; break; }
+                const size_t at = (size_t)reg * 64 + (size_t)(l + sh);
+                if (taken[at]) { ok = false; break; }                // (two steps on one lane of a register)
+                taken[at] = 1;
+                gsrc[at] = ((unsigned)kind << 28) | (unsigned)idx;
+                if (kind == 2) {
+                    if (idx >= r->nnzL || r->Lcol[idx] < 0 || r->Lcol[idx] > 0xFFFF) { ok = false; break; }
+                    glcol[at] = (unsigned short)r->Lcol[idx];
+                }
+            }
+        }
+    }
+#ifdef CPG_GENI_FAC_NSTEPS
+    if (ok) {
+        // tables of the generated factorisation: its header fixes (steps, level end, group width) per chunk and the term
+        // counts per lane (fingerprint); the operand positions and destinations are packed from the plan handed in here
+        static const int fch[][3] = CPG_GENI_FAC_CHUNKS;
+        const size_t fac_end = nx ? nd + nx + 2 : nd + 1;         // [M | 1/d (| X | 1.0) | 0.0]
+        const size_t one = nd + nx;                               // (merged programs)
+        unsigned hsh2 = 0x811C9DC5u;
+        auto mix = [&](unsigned v) { for (int k = 0; k < 4; k++) { hsh2 = (hsh2 ^ ((v >> (8 * k)) & 0xFFu)) * 0x01000193u; } };
+        ok = g.fac_chunks == CPG_GENI_FAC_NCHUNKS && fac_end - 1 == (size_t)CPG_GENI_FAC_ZERO && fac_end <= 0xFFFFu;
+#ifdef CPG_GENI_FAC_ONE
+        ok = ok && one == (size_t)CPG_GENI_FAC_ONE;
+#endif
+        for (int c = 0; ok && c < g.fac_chunks; c++) { mix((unsigned)g.fac_ctab[4 * c]); mix((unsigned)g.fac_ctab[4 * c + 1]); mix((unsigned)g.fac_ctab[4 * c + 3]); }
+        for (size_t e = 0; ok && e < (size_t)g.fac_chunks * 64; e++) mix(g.fac_len[e]);
+        ok = ok && hsh2 == CPG_GENI_FAC_FINGERPRINT;
+        if (ok) {
+            const unsigned long long Z = (unsigned long long)(fac_end - 1);
+            gtri.assign((size_t)CPG_GENI_FAC_NSTEPS * 64, Z | (Z << 16) | (Z << 32));
+            gdk.assign((size_t)g.fac_chunks * 64, 0xFFFFu);
+            gkc.assign((size_t)g.fac_chunks * 64, 0.0);
+            size_t step = 0;
+            for (int c = 0; ok && c < g.fac_chunks; c++) {
+                const int L = g.fac_ctab[4 * c];
+                size_t base = (size_t)g.fac_ctab[4 * c + 2];
+                if (L != fch[c][0]) { ok = false; break; }
+                for (int s = 0; ok && s < L; s++, step++) {
+                    int cnt = 0;
+                    for (int l = 0; l < 64; l++) {
+                        const unsigned ln = g.fac_len[(size_t)c * 64 + l];
+                        if ((int)(ln & 0xFFFFu) <= s) continue;
+                        const size_t e = base + (size_t)l;        // (lanes with entries at step s form a prefix of the chunk)
+                        if (l != cnt || e >= (size_t)g.fac_triples) { ok = false; break; }
+                        cnt++;
+                        if ((int)(ln >> 16) > s) {
+                            // a: an entry of M; b: an entry of M, or (merged) an entry of X or the 1.0; k: a reciprocal pivot
+                            const unsigned a = g.fac_a[e], b = g.fac_b[e], k = nx ? g.fac_k[e] : (unsigned)r->nnzL + g.fac_k[e];
+                            if (a >= (unsigned)r->nnzL || !(b < (unsigned)r->nnzL || (nx && b >= nd && b <= one)) ||
+                                k < (unsigned)r->nnzL || k >= nd) { ok = false; break; }
+                            gtri[step * 64 + (size_t)l] = (unsigned long long)a | ((unsigned long long)b << 16) | ((unsigned long long)k << 32);
+                        }
+                    }
+                    base += (size_t)cnt;
+                }
+                for (int l = 0; ok && l < 64; l++) {
+                    const unsigned t0 = g.fac_task[(size_t)c * 64 + l];
+                    if (t0 == 0xFFFFFFFFu) continue;
+                    const unsigned t = nx ? (t0 & 0x7FFFFFFFu) : t0;
+                    if (t >= nd + nx) { ok = false; break; }
+                    // (an X destination: no KKT value; the generated code of the inverse chunks reads neither table)
+                    const int kr = t < nd ? fkrow[t] : -1;
+                    gdk[(size_t)c * 64 + l] = t | ((unsigned)(kr + 1) << 16);
+                    gkc[(size_t)c * 64 + l] = t < nd ? fkc[t] : 0.0;
+                }
+            }
+            if (ok && step != (size_t)CPG_GENI_FAC_NSTEPS) ok = false;
+        }
+        if (ok) {
+            if ((rc = upload<unsigned long long>(h, own, gtri.data(), gtri.size(), &R.gf_tri))) return rc;
+            if ((rc = upload<unsigned>(h, own, gdk.data(), gdk.size(), &R.gf_dk))) return rc;
+            if ((rc = upload<double>(h, own, gkc.data(), gkc.size(), &R.gf_kc))) return rc;
+        }
+    }
+#else
+    ok = ok && !nx;               // (a merged program needs the generated factorisation of its header)
+#endif
+    if (ok) {
+        if ((rc = upload<unsigned short>(h, own, glcol.data(), glcol.size(), &R.gi_lcol))) return rc;
+        if ((rc = upload<unsigned short>(h, own, gcols.data(), gcols.size(), &R.gi_cols))) return rc;
+        if ((rc = upload<unsigned short>(h, own, grows.data(), grows.size(), &R.gi_rows))) return rc;
+        if ((rc = upload<unsigned>(h, own, gsrc.data(), gsrc.size(), &R.gi_src))) return rc;
+    }
+    if ((rc = rt_sync(h))) return rc;                             // (the host vectors above end here)
+    R.gi_ok = ok ? 1 : 0;
+    return CPG_OK;
+}
+#endif
+
 int cpg_hip_set_refactor(cpg_handle_t h, const cpg_osqp_refactor_t *r) {
     if (h && h->conic) { set_error("not available for a conic (interior-point) handle"); return CPG_E_BADARG; }
     if (!h || !r) { set_error("null argument"); return CPG_E_BADARG; }
@@ -1608,25 +1781,14 @@ int cpg_hip_set_refactor(cpg_handle_t h, const cpg_osqp_refactor_t *r) {
         if ((rc = upload<double>(h, own, r->E, m, &R.Es))) return rc;
         if ((rc = upload<double>(h, own, einv.data(), m, &R.Einvs))) return rc;
     }
-    R.gf_tri = nullptr; R.gf_dk = nullptr;
+    R.gf_tri = nullptr; R.gf_dk = nullptr; R.gf_kc = nullptr;
     R.gi_ok = 0; R.gi_cols = R.gi_rows = nullptr; R.gi_src = nullptr; R.gi_lcol = nullptr; R.fac_kc = nullptr; R.fac_krow = nullptr; R.fac_kc_cl = nullptr; R.fac_krow_cl = nullptr; R.fac_kind_cl = nullptr; R.fac_idx_cl = nullptr;
     std::vector<double> fkc, fkc_cl;                              // alive until the sync below
     std::vector<int> fkrow, fkrow_cl;
 
     if (r->shared_mats) {   // KKT values of the factorisation's destinations: constants of the family, except -1 / rho_vec
-        bool ok = true;
+        if (!kkt_constants(h, r, fkc, fkrow)) { set_error("cpg_hip_set_refactor: KKT source table out of range"); return CPG_E_BADARG; }
         const size_t nd = (size_t)r->nnzL + N;
-        fkc.assign(nd, 0.0); fkrow.assign(nd, -1);
-        for (size_t d = 0; ok && d < nd; d++) {
-            const int kind = r->ksrc_kind[d], idx = r->ksrc_idx[d];
-            const bool piv = d >= (size_t)r->nnzL;
-            if (kind == CPG_K_P) { if (idx < 0 || idx >= r->nnzP) ok = false; else fkc[d] = r->Ps[idx] + (piv ? h->F.sigma : 0.0); }
-            else if (kind == CPG_K_A) { if (idx < 0 || idx >= r->nnzA) ok = false; else fkc[d] = r->As[idx]; }
-            else if (kind == CPG_K_SIGMA) fkc[d] = h->F.sigma;
-            else if (kind == CPG_K_RHO) { if (idx < 0 || (size_t)idx >= m) ok = false; else fkrow[d] = idx; }
-            else if (kind != CPG_K_NONE) ok = false;
-        }
-        if (!ok) { set_error("cpg_hip_set_refactor: KKT source table out of range"); return CPG_E_BADARG; }
         fkc_cl.assign((size_t)r->fac_chunks * 64, 0.0); fkrow_cl.assign((size_t)r->fac_chunks * 64, -1);
         for (size_t e = 0; e < fkc_cl.size(); e++) {
             const unsigned t = r->fac_task[e];
@@ -1640,114 +1802,34 @@ int cpg_hip_set_refactor(cpg_handle_t h, const cpg_osqp_refactor_t *r) {
         if ((rc = upload<int>(h, own, fkrow_cl.data(), fkrow_cl.size(), &R.fac_krow_cl))) return rc;
     }
 #ifdef CPG_GENI_HEADER
-    std::vector<unsigned short> gcols, grows, glcol;
-    std::vector<unsigned> gsrc, gdk;
-    std::vector<unsigned long long> gtri;
-#ifdef CPG_GENI_N
-    const bool geni_dims = h->F.n == CPG_GENI_N && h->F.m == CPG_GENI_M && h->F.n_eq == CPG_GENI_NEQ;
-#else
-    const bool geni_dims = true;
-#endif
-    if (geni_dims && r->shared_mats && r->sol_chunks == CPG_GENI_NCHUNKS && r->sol_nnz == CPG_GENI_NNZ && r->sol_slots == CPG_GENI_NSLOTS) {
-        const unsigned hsh = program_fingerprint(r->sol_ctab, r->sol_desc, r->sol_cols, r->sol_chunks, r->sol_nnz);
-        static const int steps[][4] = CPG_GENI_STEPS;             // {first entry, active lanes, coefficient register, lane shift} in execution order
-        static const int chunk_shift[] = CPG_GENI_CHUNK_SHIFT;
-        bool ok = hsh == CPG_GENI_FINGERPRINT;
-        {   // the row programs of the termination test carry their chunk tables as literals
-            const int nn[3] = {CPG_GENI_AROWS_N, CPG_GENI_PROWS_N, CPG_GENI_ATROWS_N};
-            for (int k = 0; ok && k < 3; k++) {
-                if ((int)h->rows_hdr[k].size() != 4 * nn[k]) ok = false;
-                for (int c2 = 0; ok && c2 < nn[k]; c2++)
-                    if (h->rows_hdr[k][4 * c2] != cpg::GeniRows::len(k, c2) || h->rows_hdr[k][4 * c2 + 3] != cpg::GeniRows::off(k, c2)) ok = false;
-            }
-        }
-        if (ok) ok = generated_tables(r->sol_ctab, r->sol_desc, r->sol_cols, r->sol_chunks, r->sol_nnz, r->sol_slots, steps, CPG_GENI_NSTEPS, gcols, grows, chunk_shift);
-        if (ok) {
-            // coefficient sources per (register, lane): the steps that share a register occupy disjoint lane ranges
-            gsrc.assign((size_t)CPG_GENI_NREGS * 64, 0u);
-            glcol.assign((size_t)CPG_GENI_NREGS * 64, (unsigned short)0);
-            std::vector<char> taken((size_t)CPG_GENI_NREGS * 64, 0);
-            for (int t = 0; ok && t < CPG_GENI_NSTEPS; t++) {
-                const int e = steps[t][0], cnt = steps[t][1], reg = steps[t][2], sh = steps[t][3];
-                if (reg < 0 || reg >= CPG_GENI_NREGS) { ok = false; break; }
-                for (int l = 0; l < cnt; l++) {
-                    const int kind = r->sol_kind[e + l], idx = r->sol_idx[e + l];
-                    if (kind < 0 || kind > 3 || idx < 0 || idx >= (1 << 28)) { ok = false; break; }
-                    const size_t at = (size_t)reg * 64 + (size_t)(l + sh);
-                    if (taken[at]) { ok = false; break; }                // (two steps on one lane of a register)
-                    taken[at] = 1;
-                    gsrc[at] = ((unsigned)kind << 28) | (unsigned)idx;
-                    if (kind == 2) {
-                        if (idx >= r->nnzL || r->Lcol[idx] < 0 || r->Lcol[idx] > 0xFFFF) { ok = false; break; }
-                        glcol[at] = (unsigned short)r->Lcol[idx];
-                    }
-                }
-            }
-        }
-#ifdef CPG_GENI_FAC_NSTEPS
-        if (ok) {
-            // tables of the generated factorisation: its header fixes (steps, level end, group width) per chunk and the term
-            // counts per lane (fingerprint); the operand positions and destinations are packed from the plan handed in here
-            static const int fch[][3] = CPG_GENI_FAC_CHUNKS;
-            const size_t nd = (size_t)r->nnzL + N;
-            unsigned hsh = 0x811C9DC5u;
-            auto mix = [&](unsigned v) { for (int k = 0; k < 4; k++) { hsh = (hsh ^ ((v >> (8 * k)) & 0xFFu)) * 0x01000193u; } };
-            ok = r->fac_chunks == CPG_GENI_FAC_NCHUNKS && nd == (size_t)CPG_GENI_FAC_ZERO && nd < 0xFFFFu;
-            for (int c = 0; ok && c < r->fac_chunks; c++) { mix((unsigned)r->fac_ctab[4 * c]); mix((unsigned)r->fac_ctab[4 * c + 1]); mix((unsigned)r->fac_ctab[4 * c + 3]); }
-            for (size_t e = 0; ok && e < (size_t)r->fac_chunks * 64; e++) mix(r->fac_len[e]);
-            ok = ok && hsh == CPG_GENI_FAC_FINGERPRINT;
-            if (ok) {
-                const unsigned long long Z = (unsigned long long)nd;
-                gtri.assign((size_t)CPG_GENI_FAC_NSTEPS * 64, Z | (Z << 16) | (Z << 32));
-                gdk.assign((size_t)r->fac_chunks * 64, 0xFFFFu);
-                size_t step = 0;
-                for (int c = 0; ok && c < r->fac_chunks; c++) {
-                    const int L = r->fac_ctab[4 * c];
-                    size_t base = (size_t)r->fac_ctab[4 * c + 2];
-                    if (L != fch[c][0]) { ok = false; break; }
-                    for (int s = 0; ok && s < L; s++, step++) {
-                        int cnt = 0;
-                        for (int l = 0; l < 64; l++) {
-                            const unsigned ln = r->fac_len[(size_t)c * 64 + l];
-                            if ((int)(ln & 0xFFFFu) <= s) continue;
-                            const size_t e = base + (size_t)l;        // (lanes with entries at step s form a prefix of the chunk)
-                            if (l != cnt || e >= (size_t)r->fac_triples) { ok = false; break; }
-                            cnt++;
-                            if ((int)(ln >> 16) > s) {
-                                const unsigned a = r->fac_a[e], b = r->fac_b[e], k = r->fac_k[e];
-                                if (a >= (unsigned)r->nnzL || b >= (unsigned)r->nnzL || k >= (unsigned)N) { ok = false; break; }
-                                gtri[step * 64 + (size_t)l] = (unsigned long long)a | ((unsigned long long)b << 16) | ((unsigned long long)((unsigned)r->nnzL + k) << 32);
-                            }
-                        }
-                        base += (size_t)cnt;
-                    }
-                    for (int l = 0; ok && l < 64; l++) {
-                        const unsigned t = r->fac_task[(size_t)c * 64 + l];
-                        if (t == 0xFFFFFFFFu) continue;
-                        const int kr = fkrow_cl[(size_t)c * 64 + l];
-                        gdk[(size_t)c * 64 + l] = t | ((unsigned)(kr + 1) << 16);
-                    }
-                }
-                if (ok && step != (size_t)CPG_GENI_FAC_NSTEPS) ok = false;
-            }
-            if (ok) {
-                if ((rc = upload<unsigned long long>(h, own, gtri.data(), gtri.size(), &R.gf_tri))) return rc;
-                if ((rc = upload<unsigned>(h, own, gdk.data(), gdk.size(), &R.gf_dk))) return rc;
-            }
-        }
-#endif
-        if (ok) {
-            if ((rc = upload<unsigned short>(h, own, glcol.data(), glcol.size(), &R.gi_lcol))) return rc;
-            if ((rc = upload<unsigned short>(h, own, gcols.data(), gcols.size(), &R.gi_cols))) return rc;
-            if ((rc = upload<unsigned short>(h, own, grows.data(), grows.size(), &R.gi_rows))) return rc;
-            if ((rc = upload<unsigned>(h, own, gsrc.data(), gsrc.size(), &R.gi_src))) return rc;
-            R.gi_ok = 1;
-        }
+    if (r->shared_mats) {
+        const InstanceTables g{0, r->sol_chunks, r->sol_nnz, r->sol_slots, r->sol_ctab, r->sol_desc, r->sol_cols, r->sol_kind, r->sol_idx,
+                               r->fac_chunks, r->fac_triples, r->fac_ctab, r->fac_task, r->fac_len, r->fac_a, r->fac_b, r->fac_k};
+        if ((rc = set_instance_executor(h, r, g, fkc, fkrow))) return rc;
     }
 #endif
     if ((rc = rt_sync(h))) return rc;
     h->refactor_mode = true;
     h->have_update = true;
+    return CPG_OK;
+}
+
+int cpg_hip_set_refactor_merged(cpg_handle_t h, const cpg_osqp_refactor_t *r, const cpg_osqp_resident_t *mg) {
+    if (h && h->conic) { set_error("not available for a conic (interior-point) handle"); return CPG_E_BADARG; }
+    if (!h || !r || !mg) { set_error("null argument"); return CPG_E_BADARG; }
+    if (!r->shared_mats || mg->nnzX <= 0) { set_error("cpg_hip_set_refactor_merged: needs shared-matrix tables and a merged program"); return CPG_E_BADARG; }
+    int rc = cpg_hip_set_refactor(h, r);
+    if (rc) return rc;
+#ifdef CPG_GENI_NNZX
+    if (mg->nnzX == CPG_GENI_NNZX) {
+        std::vector<double> fkc;
+        std::vector<int> fkrow;
+        if (!kkt_constants(h, r, fkc, fkrow)) { set_error("cpg_hip_set_refactor_merged: KKT source table out of range"); return CPG_E_BADARG; }
+        const InstanceTables g{mg->nnzX, mg->sol_chunks, mg->sol_nnz, mg->sol_slots, mg->sol_ctab, mg->sol_desc, mg->sol_cols, mg->sol_kind,
+                               mg->sol_idx, mg->fac_chunks, mg->fac_triples, mg->f_ctab, mg->f_task, mg->f_len, mg->f_a, mg->f_b, mg->f_k};
+        if ((rc = set_instance_executor(h, r, g, fkc, fkrow))) return rc;
+    }
+#endif
     return CPG_OK;
 }
 

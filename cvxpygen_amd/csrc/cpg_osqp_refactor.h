@@ -85,7 +85,8 @@ struct DevRefactor {
     // uploaded program is the one the library was generated for): operand byte offsets of all 64 lanes of every
     // step, four steps side by side ([step / 4][lane][4]; idle lanes: the zero slot), output slot | segment mask << 13
     // of every (chunk, lane), four chunks side by side, and per (step, lane) where the coefficient comes from
-    // (kind << 28 | index; kind 1: 1.0, 2: -L[index], 3: 1 / d[index], 0: none).
+    // (kind << 28 | index; kind 1: 1.0, 2: -L[index], 3: 1 / d[index] -- index N + x: entry x of a merged program's block
+    // inverses, which follow 1 / d in the factor --, 0: none).
     int gi_ok;
     const unsigned short *gi_cols, *gi_rows;
     const unsigned *gi_src;
@@ -94,6 +95,7 @@ struct DevRefactor {
     // a | b << 16 | k << 32 per (step, lane), destination | (rho row + 1) << 16 per (chunk, lane); see codegen.emit_factor_program
     const unsigned long long *gf_tri;
     const unsigned *gf_dk;
+    const double *gf_kc;                // KKT constant per (chunk, lane) of THAT schedule (fac_kc_cl, or the merged schedule's)
     // generated streaming executor (run_program_gens of cpg_stream_<name>.h, per-instance-matrix mode): operand offsets
     // [step / 4][lane][4] and output slots [chunk / 4][lane][4] in global memory; the coefficients stay in program-entry order
     const unsigned short *gs_cols, *gs_rows;
@@ -531,7 +533,8 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
     // slice holds the factor (M [nnzL] | 1 / d [N]) while numeric_ldl_lds runs -- nothing in it is live then
     size_t per_wave = (size_t)ldw + (GENI ? (size_t)(N + (N & 1u)) : 0u);
 #ifdef CPG_GENI_FAC_NSTEPS
-    const size_t fac_doubles = (size_t)R.nnzL + N + 1u;       // (+ the zero slot idle lanes of the generated factorisation read)
+    // (+ the zero slot idle lanes of the generated factorisation read; a merged program: [M | 1/d | X | 1.0 | 0.0], see below)
+    const size_t fac_doubles = (size_t)CPG_GENI_FAC_ZERO + 1u;
 #else
     const size_t fac_doubles = (size_t)R.nnzL + N;
 #endif
@@ -731,8 +734,13 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
             cpgw::mem_order();                // B.rinv
 #ifdef CPG_GENI_FAC_NSTEPS
             if (lane == 0) w[CPG_GENI_FAC_ZERO] = 0.0;
+#ifdef CPG_GENI_FAC_ONE
+            // merged program (refactor_plan.shared_mode_plan): the factorisation goes on to X = L_GG^-1 of every merged level
+            // group, whose dot products read the unit diagonal here; coefficients of kind 3 with index >= N are X entries
+            if (lane == 0) w[CPG_GENI_FAC_ONE] = 1.0;
+#endif
             cpgw::lds_order();
-            numeric_ldl_gen(R.gf_tri, R.gf_dk, R.fac_kc_cl, (const double *)B.rinv, w, lane);
+            numeric_ldl_gen(R.gf_tri, R.gf_dk, R.gf_kc, (const double *)B.rinv, w, lane);
 #else
             numeric_ldl_m<true>(R, w, w + R.nnzL, (const double *)B.rinv, lane);
 #endif

@@ -134,6 +134,10 @@ class RefactorPlan:
     sol: _sp.RaggedProgram
     sol_kind: np.ndarray; sol_idx: np.ndarray
     stats: Dict[str, float]
+    # shared-matrix mode: the MERGED variant of this plan the generated instance executor runs (resident_plan.ResidentPlan:
+    # level groups, their diagonal blocks inverted on the device, value sources SRC_X), or None; the tables above stay the
+    # plain plan's -- what the streaming executor of the same handle runs
+    merged: Optional[object] = None
 
 
 # forward_in_place='auto': the forward sweep drops its unit-diagonal entries (8 streamed bytes per row
@@ -269,18 +273,43 @@ def build_schedules(N: int, perm: np.ndarray, Lp: np.ndarray, Li: np.ndarray, sr
 INSTANCE_STAGE_SCALE = float(os.environ.get('CPG_INSTANCE_STAGE_SCALE', 0.7))
 
 
-def shared_mode_plan(Ps: sp.csc_matrix, As: sp.csc_matrix, osqp: _setup.OsqpPlan) -> 'RefactorPlan':
+def shared_mode_plan(Ps: sp.csc_matrix, As: sp.csc_matrix, osqp: _setup.OsqpPlan, merge: bool = True) -> 'RefactorPlan':
     """The refactorisation plan of shared-matrix mode (rho adaptation hand-over, rows that changed class).  Planned for
     the generated instance executor (INSTANCE_STAGE_SCALE) when the resulting program fits it -- coefficient registers,
     LDS tables: codegen.instance_program_fits --, else as every streaming plan.  Used by BOTH the code generator
     (codegen.instance_header) and the runtime (BatchSolver._ensure_refactor_handle): the library checks the program's
-    fingerprint."""
+    fingerprint.
+    merge: the generated executor's program may be the merged variant (`merged`): consecutive narrow levels in groups of at
+    most resident_plan.INSTANCE_MAX_GROUP_ROWS rows, each group's diagonal block inverted per instance on the device --
+    two dependent phases per group and sweep instead of one per level (MPC 12/4/10: 35 levels, 30 of them 4 - 6 rows of
+    the horizon chain).  Only when that program fits the executor as well; else the plain one."""
     from . import codegen as _cg
     if INSTANCE_STAGE_SCALE != STREAM_STAGE_SCALE:
         cand = build_refactor_plan(Ps, As, osqp, stage_scale=INSTANCE_STAGE_SCALE)
         if _cg.instance_program_fits(cand):
+            if merge:
+                mg = _merged_variant(cand, Ps, As, osqp)
+                if mg is not None and _cg.instance_program_fits(mg):
+                    return mg
             return cand
     return build_refactor_plan(Ps, As, osqp)
+
+
+def _merged_variant(cand: RefactorPlan, Ps, As, osqp) -> Optional[RefactorPlan]:
+    """cand with the merged program of resident_plan (groups of at most INSTANCE_MAX_GROUP_ROWS rows, the products with
+    the block inverses in place: the solution stays in the slots of the plain program); None when nothing merges"""
+    import dataclasses
+    from . import resident_plan as _rs
+    cap = _rs.INSTANCE_MAX_GROUP_ROWS
+    if cap <= 1:
+        return None
+    groups = _rs.plan_groups(cand.n + cand.m, cand.Lp, cand.Li, cap)
+    if all(a == b for a, b in groups):
+        return None
+    mg = _rs.build_resident_plan(Ps, As, osqp, stage_scale=INSTANCE_STAGE_SCALE, groups=groups, inplace_x=True)
+    stats = dict(cand.stats, groups=len(groups), merged=sum(1 for a, b in groups if a != b), nnzX=mg.nnzX,
+                 merged_phases=mg.sol.n_phases, merged_steps=int(mg.sol.ctab[:, 0].sum()), fac_len=mg.fac_len)
+    return dataclasses.replace(cand, merged=mg, stats=stats)
 
 
 def build_refactor_plan(P: sp.csc_matrix, A: sp.csc_matrix, osqp: _setup.OsqpPlan, stage_scale: Optional[float] = None) -> RefactorPlan:

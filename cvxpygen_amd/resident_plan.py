@@ -43,6 +43,10 @@ from . import solve_program as _sp
 LANES = 64
 SRC_ZERO, SRC_ONE, SRC_NEG_L, SRC_DINV, SRC_X = 0, 1, 2, 3, 4
 MAX_GROUP_ROWS = int(os.environ.get('CPG_RESIDENT_MAX_GROUP_ROWS', 64))
+# the same limit for the merged program of shared-matrix mode's generated instance executor (refactor_plan.shared_mode_plan;
+# 0: no merging).  MPC 12/4/10: 32 is the largest cap whose program still fits 64 coefficient registers and whose factor
+# [M | 1/d | X] fits eight LDS slices -- 11 groups, 33 instead of 69 dependent phases per KKT solve, 81 instead of 165 steps
+INSTANCE_MAX_GROUP_ROWS = int(os.environ.get('CPG_INSTANCE_MAX_GROUP_ROWS', 32))
 # what the planner charges for a reduction stage relative to a multiply-add step (refactor_plan.INSTANCE_STAGE_SCALE:
 # the register-resident executor is a chain of latencies)
 RESIDENT_STAGE_SCALE = float(os.environ.get('CPG_RESIDENT_STAGE_SCALE', 0.7))

@@ -136,7 +136,7 @@ class CpgLibrary:
 
     SYMBOLS = ['cpg_hip_device_count', 'cpg_hip_create_osqp', 'cpg_hip_create_clarabel', 'cpg_hip_destroy', 'cpg_hip_last_error',
                'cpg_hip_status_string', 'cpg_hip_set_default_settings', 'cpg_hip_set_setting',
-               'cpg_hip_get_setting', 'cpg_hip_set_build_option', 'cpg_hip_set_handover', 'cpg_hip_last_phase_ms', 'cpg_hip_set_update', 'cpg_hip_set_refactor', 'cpg_hip_set_resident', 'cpg_hip_set_gradient', 'cpg_hip_gradient_batch',
+               'cpg_hip_get_setting', 'cpg_hip_set_build_option', 'cpg_hip_set_handover', 'cpg_hip_last_phase_ms', 'cpg_hip_set_update', 'cpg_hip_set_refactor', 'cpg_hip_set_refactor_merged', 'cpg_hip_set_resident', 'cpg_hip_set_gradient', 'cpg_hip_gradient_batch',
                'cpg_hip_solve_batch',
                'cpg_hip_solve_batch_device', 'cpg_hip_solve_batch_state', 'cpg_hip_solve_batch_device_state', 'cpg_hip_solve_batches_pipelined', 'cpg_hip_host_malloc',
                'cpg_hip_host_free', 'cpg_hip_synchronize', 'cpg_hip_get_stream', 'cpg_hip_last_kernel_ms',
@@ -167,6 +167,7 @@ class CpgLibrary:
         L.cpg_hip_set_update.argtypes = [C.c_void_p, C.POINTER(_Update)]
         L.cpg_hip_set_refactor.argtypes = [C.c_void_p, C.POINTER(_Refactor)]
         L.cpg_hip_set_resident.argtypes = [C.c_void_p, C.POINTER(_Refactor), C.POINTER(_Resident)]
+        L.cpg_hip_set_refactor_merged.argtypes = [C.c_void_p, C.POINTER(_Refactor), C.POINTER(_Resident)]
         L.cpg_hip_set_gradient.argtypes = [C.c_void_p, C.POINTER(_Gradient)]
         L.cpg_hip_gradient_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp]
         L.cpg_hip_solve_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]
@@ -569,12 +570,16 @@ class BatchSolver:
             # The plan codegen.instance_header generated the library's instance executor from (planned for register-
             # resident coefficients: more, narrower steps) -- when this library has one for this family: its
             # cpg_instance_<name>.h sits next to it.  Any other library streams the program, and gets the streaming plan.
+            # The header holds the merged program when the plan has one (its fingerprint differs from the plain one's); a
+            # library generated before the merge, or with it switched off, carries the plain program and keeps it.
             rplan = None
             fps = _instance_fingerprints(self.lib.path)
             if fps:
                 cand = _rp.shared_mode_plan(Ps, As, o)
-                if cand.sol.fingerprint() in fps:
+                if cand.merged is not None and cand.merged.sol.fingerprint() in fps:
                     rplan = cand
+                elif cand.sol.fingerprint() in fps:
+                    rplan = dataclasses.replace(cand, merged=None)
             if rplan is None:
                 rplan = _rp.build_refactor_plan(Ps, As, o)
             self._rplan_s = rplan
@@ -759,7 +764,19 @@ class BatchSolver:
             map_P=MP, map_A=MA, map_q=Mq, map_u=Mu, map_d=Md, q_setup=_d(q_setup),
             shared_mats=int(bool(shared_mats)), Ps=_d(Ps), As=_d(As), D=_d(Dv), E=_d(Ev), c=float(o.scaling.c))
         res = getattr(self, '_rplan_res', None) if mode == 'struct' else None
-        if res is not None:
+        mg = rp.merged if shared_mats else None
+        if mg is not None:
+            # the merged program of the generated instance executor next to the plain tables above (the streaming executor's);
+            # the termination test's row programs of a resident plan play no part here
+            none = _RowsProgram(0, 0, None, None, None, None)
+            ms = _Resident(
+                nnzX=mg.nnzX, fac_chunks=int(mg.f_ctab.shape[0]), fac_triples=len(mg.f_a), f_ctab=i32(mg.f_ctab),
+                f_task=u32(mg.f_task), f_len=u32(mg.f_len), f_a=u32(mg.f_a), f_b=u32(mg.f_b), f_k=u32(mg.f_k),
+                sol_chunks=mg.sol.n_chunks, sol_nnz=mg.sol.nnz, sol_slots=mg.sol.n_slots, sol_ctab=i32(mg.sol.ctab),
+                sol_desc=u32(mg.sol.desc), sol_cols=u16(mg.sol.cols), sol_kind=i32(mg.sol_kind), sol_idx=i32(mg.sol_idx),
+                sol_lcol=i32(mg.sol_lcol), rows_A=none, rows_P=none, rows_At=none, out_ax=0, out_px=0, out_aty=0)
+            self.lib.check(self.lib.L.cpg_hip_set_refactor_merged(hh, C.byref(rf), C.byref(ms)), 'cpg_hip_set_refactor_merged')
+        elif res is not None:
             def rows(prog, ent):
                 return _RowsProgram(n_chunks=prog.n_chunks, nnz=prog.nnz, ctab=i32(prog.ctab), desc=u32(prog.desc), cols=u16(prog.cols), ent=i32(ent))
             rs = _Resident(

@@ -326,6 +326,14 @@ int cpg_hip_set_update(cpg_handle_t h, const cpg_osqp_update_t *upd);
  * is called again */
 int cpg_hip_set_refactor(cpg_handle_t h, const cpg_osqp_refactor_t *rf);
 
+/* cpg_hip_set_refactor(h, rf) for a shared-matrix handle (rf->shared_mats), and -- when this library's generated instance
+ * executor runs the MERGED program of exactly this family (cvxpygen_amd.refactor_plan.shared_mode_plan: level groups whose
+ * diagonal blocks are inverted per instance; the header defines CPG_GENI_NNZX, the program's fingerprint decides) -- that
+ * executor's tables from mg: its f_* and sol_* fields as in cpg_osqp_resident_t (rows_* and out_* unused).  rf keeps the
+ * plain plan of the streaming executor.  Any other library keeps what cpg_hip_set_refactor chose and returns CPG_OK;
+ * cpg_hip_get_setting(h, "generated_instance_executor") reports which. */
+int cpg_hip_set_refactor_merged(cpg_handle_t h, const cpg_osqp_refactor_t *rf, const cpg_osqp_resident_t *mg);
+
 /* cpg_hip_set_refactor(h, rf), and -- when this library carries the generated resident executor of exactly this
  * family (cvxpygen_amd.codegen.resident_header; the merged program's fingerprint decides) -- the resident kernel's
  * tables: solves then run cpg_osqp_resident.h instead of the streaming kernel.  cpg_hip_get_setting(h,
