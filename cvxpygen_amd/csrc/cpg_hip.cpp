@@ -71,8 +71,15 @@ struct cpg_solver_s {
     DevBuf g_theta, g_x, g_y, g_dprim, g_dtheta;
     cpg::DevSettings S{};
     int waves_per_block = 0, inst_per_wave = 1, blocks_per_cu = 0;
-    int program_in_lds = -1;            // -1 auto, 0 stream from L2/HBM, 1 resident in LDS, 3 squad executor (program in registers)
+    int program_in_lds = -1;            // -1 auto, 0 stream from L2/HBM, 1 resident in LDS, 3 squad executor (program in registers),
+                                        // 4 register executor (merged instance program, family coefficients in registers)
     bool squad_ok = false;              // family library with this family's squad executor (cpg_osqp_squad.h)
+    // register executor of the shared kernel (cpg_hip_set_shared_registers): its device tables, and the rho / sigma its
+    // coefficients were computed at -- a solve uses them only while F.rho / F.sigma are still those
+    cpg::DevShRegs SRg{};
+    bool sreg_ok = false;
+    double sreg_rho = 0.0, sreg_sigma = 0.0;
+    std::vector<void *> sreg_owned;
     int num_cu = 256;
     size_t lds_limit = 160 * 1024;
     unsigned *d_counter = nullptr;
@@ -336,6 +343,17 @@ osqp_instance_kernel(cpg::DevFamily F, cpg::DevRefactor R, cpg::DevSettings S, c
     const int wave_global = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     cpg::osqp_refactor_body<NSX, NSZ, true>(F, R, S, Bt, cpg_lds, wave_global);
 }
+#ifdef CPG_GENI_NNZX
+// shared-factor kernel with the merged instance program as its executor (osqp_shared_body<.., SharedRegExec>): one
+// workgroup of up to eight wavefronts per CU, two per SIMD -- the coefficient registers stay live through the instance loop
+template <int NSX, int NSZ, int NV>
+__global__ void __launch_bounds__(512, 2)
+osqp_shared_reg_kernel(cpg::DevFamily F, cpg::DevUpdate U, cpg::DevSettings S, cpg::DevBatch Bt, cpg::DevShRegs RG) {
+    extern __shared__ __attribute__((aligned(16))) double cpg_lds[];
+    const int wave_global = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    cpg::osqp_shared_body<NSX, NSZ, NV, 1, false, cpg::SharedRegExec>(F, U, S, Bt, cpg_lds, wave_global, RG);
+}
+#endif
 #endif
 #ifdef CPG_GENR_HEADER
 // resident per-instance factor kernel (cpg_osqp_resident.h): at most four wavefronts per workgroup and ONE workgroup per
@@ -491,6 +509,34 @@ static int launch_squad(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, siz
     set_error("no compiled squad kernel for this family size");
     return CPG_E_UNSUPPORTED;
 }
+#endif
+
+#if defined(CPG_GENI_HEADER) && defined(CPG_GENI_NNZX)
+// the register executor's launch: waves per workgroup (cpg_hip_set_launch, at most eight), LDS = base vectors | offset and
+// output-slot tables | coefficients read from LDS | one work vector per wavefront (codegen.shared_register_lds_bytes)
+static int shared_reg_waves(cpg_handle_t h) { return h->waves_per_block > 0 && h->waves_per_block < 8 ? h->waves_per_block : 8; }
+static size_t shared_reg_lds(cpg_handle_t h, int W) {
+    const size_t tab = (size_t)(((CPG_GENI_NSTEPS + 3) / 4) * 256 + ((CPG_GENI_NCHUNKS + 3) / 4) * 256) * sizeof(unsigned short);
+    return (size_t)(h->F.n + h->F.m) * sizeof(double) + tab + (size_t)cpg::SharedRegExec::nlds * 64 * sizeof(double) +
+           (size_t)W * (CPG_GENI_NSLOTS + CPG_GEN_EXTRA_SLOTS) * sizeof(double);
+}
+// installed coefficients of the handle's current rho and sigma (never stale ones), one instance per wavefront, LDS fits
+static bool shared_reg_usable(cpg_handle_t h) {
+    return !h->refactor_mode && !h->conic && h->sreg_ok && h->sreg_rho == h->F.rho && h->sreg_sigma == h->F.sigma &&
+           h->inst_per_wave == 1 && shared_reg_lds(h, shared_reg_waves(h)) <= h->lds_limit;
+}
+static int launch_shared_reg(cpg_handle_t h, const cpg::DevBatch &Bt, int blocks, int waves, size_t lds) {
+    const int nsx = (h->F.n + 63) / 64, nsz = (h->F.m + 63) / 64, nv = vary_slots(h);
+#define Y(a, b, v, g, wm)                                                                         \
+    if (nsx <= a && nsz <= b && (nv <= v || (v >= a && v >= b)) && g == 1)                        \
+        return launch_kernel(osqp_shared_reg_kernel<a, b, v>, blocks, waves * 64, lds, h->stream, h->F, h->U, h->S, Bt, h->SRg);
+    CPG_KERNELS_LDS(Y)
+#undef Y
+    set_error("no compiled register-executor kernel for this family size");
+    return CPG_E_UNSUPPORTED;
+}
+#else
+static bool shared_reg_usable(cpg_handle_t) { return false; }
 #endif
 
 // ------------------------------------------------------------------------------------ solve dispatch
@@ -719,6 +765,23 @@ static int solve_shared(cpg_handle_t h, cpg::DevBatch &Bt) {
     }
 #endif
     if (h->program_in_lds == 3) { set_error("this library carries no squad executor for the family (cpg_hip_set_program_placement(3))"); return CPG_E_UNSUPPORTED; }
+    if (h->program_in_lds == -1 || h->program_in_lds == 4) {
+#if defined(CPG_GENI_HEADER) && defined(CPG_GENI_NNZX)
+        if (shared_reg_usable(h)) {
+            // register executor: the merged program, the family's coefficients in registers; one workgroup per CU
+            const int W = shared_reg_waves(h);
+            const size_t lds_r = shared_reg_lds(h, W);
+            const int blocks = grid_blocks(h, Bt.B, W, 1);
+            return shared_launches(h, Bt, two_phase, [&](const cpg::DevBatch &b) { return launch_shared_reg(h, b, blocks, W, lds_r); });
+        }
+#endif
+        if (h->program_in_lds == 4) {
+            set_error("no register executor for this handle (cpg_hip_set_program_placement(4)): the library carries no merged instance "
+                      "program of the family, cpg_hip_set_shared_registers was not called for its rho / sigma, two instances per "
+                      "wavefront were asked for, or its LDS need exceeds the device limit");
+            return CPG_E_UNSUPPORTED;
+        }
+    }
 #if defined(CPG_GEN_HEADER) && defined(CPG_GEN_N)
     const size_t per_wave = (size_t)G * (h->F.n_slots + CPG_GEN_EXTRA_SLOTS) * sizeof(double);
 #else
@@ -966,6 +1029,7 @@ int cpg_hip_get_setting(cpg_handle_t h, const char *name, double *v) {
     else if (s == "adaptive_rho_tolerance") *v = h->S.adaptive_rho_tolerance;
     else if (s == "check_dualgap") *v = h->S.check_dualgap;
     // (read-only facts about the handle) 1: per-instance solves of this handle run the generated instance executor
+    else if (s == "register_executor") *v = (h->program_in_lds == -1 || h->program_in_lds == 4) && shared_reg_usable(h) ? 1.0 : 0.0;
     else if (s == "squad_executor") *v = (!h->refactor_mode && !h->conic && h->squad_ok && h->program_in_lds == 3 && h->inst_per_wave == 1) ? 1.0 : 0.0;
     else if (s == "team_executor") {
         // wavefronts per instance of the team kernel this handle's per-instance solves run on; 0: another kernel (no team plan, the
@@ -1476,7 +1540,7 @@ int cpg_hip_destroy(cpg_handle_t h) {
     if (!h) return CPG_OK;
     rt_set_device(h->device);
     rt_sync(h);
-    free_list(h->owned); free_list(h->update_owned); free_list(h->refactor_owned); free_list(h->resident_owned); free_list(h->gradient_owned);
+    free_list(h->owned); free_list(h->update_owned); free_list(h->refactor_owned); free_list(h->sreg_owned); free_list(h->resident_owned); free_list(h->gradient_owned);
     free_buf(h->g_theta); free_buf(h->g_x); free_buf(h->g_y); free_buf(h->g_dprim); free_buf(h->g_dtheta);
     if (h->d_counter) rt_free(h->d_counter);
     free_buf(h->scratch);
@@ -1829,6 +1893,58 @@ int cpg_hip_set_refactor_merged(cpg_handle_t h, const cpg_osqp_refactor_t *r, co
                                mg->sol_idx, mg->fac_chunks, mg->fac_triples, mg->f_ctab, mg->f_task, mg->f_len, mg->f_a, mg->f_b, mg->f_k};
         if ((rc = set_instance_executor(h, r, g, fkc, fkrow))) return rc;
     }
+#endif
+    return CPG_OK;
+}
+
+int cpg_hip_set_shared_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, const double *coef, int32_t n_coef, double rho, double sigma) {
+    if (h && h->conic) { set_error("not available for a conic (interior-point) handle"); return CPG_E_BADARG; }
+    if (!h || !mg || !coef) { set_error("null argument"); return CPG_E_BADARG; }
+    if (h->refactor_mode) { set_error("cpg_hip_set_shared_registers: needs a shared-factor handle"); return CPG_E_BADARG; }
+    h->sreg_ok = false;
+    h->SRg = cpg::DevShRegs{};
+    int rc = rt_sync(h);                                          // (a solve in flight may still read the old tables)
+    if (rc) return rc;
+    free_list(h->sreg_owned);
+#if defined(CPG_GENI_HEADER) && defined(CPG_GENI_NNZX)
+#ifdef CPG_GENI_N
+    const bool geni_dims = h->F.n == CPG_GENI_N && h->F.m == CPG_GENI_M && h->F.n_eq == CPG_GENI_NEQ;
+#else
+    const bool geni_dims = true;
+#endif
+    if (!(geni_dims && mg->nnzX == CPG_GENI_NNZX && mg->sol_chunks == CPG_GENI_NCHUNKS && mg->sol_nnz == CPG_GENI_NNZ &&
+          mg->sol_slots == CPG_GENI_NSLOTS && n_coef == mg->sol_nnz))
+        return CPG_OK;
+    if (program_fingerprint(mg->sol_ctab, mg->sol_desc, mg->sol_cols, mg->sol_chunks, mg->sol_nnz) != CPG_GENI_FINGERPRINT) return CPG_OK;
+    static const int steps[][4] = CPG_GENI_STEPS;                 // {first entry, active lanes, coefficient register, lane shift}
+    static const int chunk_shift[] = CPG_GENI_CHUNK_SHIFT;
+    std::vector<unsigned short> gcols, grows;
+    if (!generated_tables(mg->sol_ctab, mg->sol_desc, mg->sol_cols, mg->sol_chunks, mg->sol_nnz, mg->sol_slots, steps, CPG_GENI_NSTEPS,
+                          gcols, grows, chunk_shift))
+        return CPG_OK;
+    // the coefficient of every (register, lane), laid out as load_instance_coefficients fills cf: idle lanes hold 0.0
+    std::vector<double> cf((size_t)CPG_GENI_NREGS * 64, 0.0);
+    std::vector<char> taken(cf.size(), 0);
+    for (int t = 0; t < CPG_GENI_NSTEPS; t++) {
+        const int e = steps[t][0], cnt = steps[t][1], reg = steps[t][2], sh = steps[t][3];
+        if (reg < 0 || reg >= CPG_GENI_NREGS) return CPG_OK;
+        for (int l = 0; l < cnt; l++) {
+            const size_t at = (size_t)reg * 64 + (size_t)(l + sh);
+            if (taken[at]) return CPG_OK;                         // (two steps on one lane of a register)
+            taken[at] = 1;
+            cf[at] = coef[e + l];
+        }
+    }
+    cpg::DevShRegs T{};
+    if ((rc = upload<double>(h, h->sreg_owned, cf.data(), cf.size(), &T.cf))) return rc;
+    if ((rc = upload<unsigned short>(h, h->sreg_owned, gcols.data(), gcols.size(), &T.cols))) return rc;
+    if ((rc = upload<unsigned short>(h, h->sreg_owned, grows.data(), grows.size(), &T.rows))) return rc;
+    if ((rc = rt_sync(h))) return rc;                             // (the host vectors above end here)
+    h->SRg = T;
+    h->sreg_ok = true;
+    h->sreg_rho = rho; h->sreg_sigma = sigma;
+#else
+    (void)n_coef; (void)rho; (void)sigma;
 #endif
     return CPG_OK;
 }
@@ -2433,7 +2549,7 @@ int cpg_hip_set_launch(cpg_handle_t h, int waves_per_block, int inst_per_wave, i
 }
 
 int cpg_hip_set_program_placement(cpg_handle_t h, int in_lds) {
-    if (!h || in_lds < -1 || in_lds > 3) { set_error("in_lds must be -1, 0, 1, 2 or 3"); return CPG_E_BADARG; }
+    if (!h || in_lds < -1 || in_lds > 4) { set_error("in_lds must be -1, 0, 1, 2, 3 or 4"); return CPG_E_BADARG; }
     h->program_in_lds = in_lds;
     return CPG_OK;
 }

@@ -967,21 +967,41 @@ CPG_DEV void hand_over(const DevFamily &F, const DevBatch &Bt, const double (&Ix
 #define CPG_ROW_CLASS(s) ((int)ct[s])
 #endif
 
+// Register executor of the shared kernel (cpg_hip_set_shared_registers): the family library's merged instance program
+// (run_program_inst of cpg_instance_<name>.h) with the coefficients of the family's factor.  Device tables: the
+// coefficients [NREGS][64] at the handle's rho / sigma, operand offsets [step / 4][lane][4], output slots [chunk / 4][lane][4].
+struct DevShRegs {
+    const double *cf;
+    const unsigned short *cols, *rows;
+};
+// no register executor: the LDS-resident or streamed program
+struct NoRegExec {
+    static constexpr bool active = false;
+    static constexpr int nslots = 1;
+    CPG_DEV explicit NoRegExec(const DevShRegs &) {}
+    CPG_DEV size_t stage(double *) { return 0; }
+    CPG_DEV void load(int) {}
+    CPG_DEV void run(double *, int) const {}
+};
+
 // ------------------------------------------------------------------------------------ the kernel body
-template <int NSX, int NSZ, int NV, int G, bool LDSPROG>
+// REG: NoRegExec, or the register executor (SharedRegExec, cpg_osqp_refactor.h; G = 1): its program solves in place in
+// canonical order, so the right-hand side goes to, and the solution comes from, the canonical position of every owned entry
+template <int NSX, int NSZ, int NV, int G, bool LDSPROG, typename REG = NoRegExec>
 CPG_DEV void osqp_shared_body(const DevFamily &F, const DevUpdate &U, const DevSettings &S,
-                              const DevBatch &Bt, double *lds, int wave_global) {
+                              const DevBatch &Bt, double *lds, int wave_global, const DevShRegs &RG = DevShRegs{}) {
     typedef Inst<NSX, NSZ, NV> InstT;
+    static_assert(!REG::active || (G == 1 && !LDSPROG), "the register executor serves one instance per wavefront");
     const int lane0 = cpgw::lane_id();
     const int lane = lane0;
 #if defined(CPG_GEN_N)
     // family-specialised build: dimensions are literals, so the bounds checks of full slots fold away
     constexpr unsigned n_c = GenFam::n, m_c = GenFam::m;
-    constexpr int ldw = GenFam::n_slots + CPG_GEN_EXTRA_SLOTS;   // + dummy store targets and the zero slot
+    constexpr int ldw = REG::active ? REG::nslots : GenFam::n_slots + CPG_GEN_EXTRA_SLOTS;   // + dummy store targets and the zero slot
     static_assert(!LDSPROG || ((n_c + 63) / 64 == (unsigned)NSX && (m_c + 63) / 64 == (unsigned)NSZ), "slot class of the generated family");
 #else
     const unsigned n_c = (unsigned)F.n, m_c = (unsigned)F.m;
-    const int ldw = F.n_slots;
+    const int ldw = REG::active ? REG::nslots : F.n_slots;
 #endif
     const int N = F.n + F.m;
     // block-shared copy of the family's base vectors, then one work vector per instance
@@ -1037,22 +1057,33 @@ CPG_DEV void osqp_shared_body(const DevFamily &F, const DevUpdate &U, const DevS
         LP.ctab = lt; LP.desc = ld; LP.rows16 = nullptr;
 #endif
     }
+    REG rg(RG);
+    lds_off += rg.stage(lds + lds_off);       // (its offset / output-slot tables)
     cpgw::block_sync();
+    rg.load(lane);                            // coefficients: registers for the whole instance loop
     double *w = lds + lds_off + (size_t)cpgw::wave_in_block() * G * ldw;
     (void)wave_global;
     const long long ngroups = (Bt.B + G - 1) / G;
     const double rho_eq = 1e3 * F.rho, rho_in = F.rho, rho_fr = 1e-6;
     const double ri_eq = 1.0 / rho_eq, ri_in = 1.0 / rho_in, ri_fr = 1.0 / rho_fr;
-    // family constants kept in registers: row class and final LDS slot of every owned entry
+    // family constants kept in registers: row class and final LDS slot of every owned entry (the register executor: its
+    // canonical position, where the right-hand side goes in as well)
     signed char ct_reg[NSZ];
     unsigned short fpx[NSX], fpz[NSZ];
 #pragma unroll
-    for (int s = 0; s < NSX; s++) { const unsigned i = (unsigned)lane + 64u * (unsigned)s; fpx[s] = (i < (unsigned)F.n) ? cpgw::gld(F.fpos, i) : 0; }
+    for (int s = 0; s < NSX; s++) {
+        const unsigned i = (unsigned)lane + 64u * (unsigned)s;
+        fpx[s] = 0;
+        if (i < (unsigned)F.n) fpx[s] = !REG::active ? cpgw::gld(F.fpos, i) : (unsigned short)(F.ord ? (unsigned)cpgw::gld(F.ord, i) : i);
+    }
 #pragma unroll
     for (int s = 0; s < NSZ; s++) {
         const unsigned i = (unsigned)lane + 64u * (unsigned)s;
         ct_reg[s] = (i < (unsigned)F.m) ? cpgw::gld(F.ctype, i) : 0;
-        fpz[s] = (i < (unsigned)F.m) ? cpgw::gld(F.fpos, (unsigned)F.n + i) : 0;
+        fpz[s] = 0;
+        if (i < (unsigned)F.m)
+            fpz[s] = !REG::active ? cpgw::gld(F.fpos, (unsigned)F.n + i)
+                                  : (unsigned short)((unsigned)F.n + (F.ord ? (unsigned)cpgw::gld(F.ord, (unsigned)F.n + i) : i));
     }
 
     for (;;) {
@@ -1121,7 +1152,7 @@ CPG_DEV void osqp_shared_body(const DevFamily &F, const DevUpdate &U, const DevS
 #pragma unroll
                 for (int s = 0; s < NSX; s++) {
                     const unsigned i = (unsigned)lane + 64u * (unsigned)s;
-                    if (i < n_c) wg[i] = F.sigma * I[g].x[s] - SharedCtx<NSX, NSZ, NV>{F, sh, shu, I[g], wg, lane}.q(s, i);
+                    if (i < n_c) wg[REG::active ? (unsigned)fpx[s] : i] = F.sigma * I[g].x[s] - SharedCtx<NSX, NSZ, NV>{F, sh, shu, I[g], wg, lane}.q(s, i);
                     CPG_FENCE_EVERY(s);
                 }
 #pragma unroll
@@ -1129,11 +1160,13 @@ CPG_DEV void osqp_shared_body(const DevFamily &F, const DevUpdate &U, const DevS
                     const unsigned i = (unsigned)lane + 64u * (unsigned)s;
                     const int cts = CPG_ROW_CLASS(s);
                     const double ri = cts == 1 ? ri_eq : (cts == 0 ? ri_in : ri_fr);
-                    if (i < m_c) wg[n_c + i] = I[g].z[s] - ri * I[g].y[s];
+                    if (i < m_c) wg[REG::active ? (unsigned)fpz[s] : n_c + i] = I[g].z[s] - ri * I[g].y[s];
                     CPG_FENCE_EVERY(s);
                 }
             }
             cpgw::lds_order();
+            if (REG::active) rg.run(w, lane);
+            else
 #ifdef CPG_GEN_HEADER
             if (LDSPROG) run_program_gen<G>(LP.vals, LP.cols, LP.rows16, w, ldw, lane);
 #else
@@ -1241,7 +1274,9 @@ CPG_DEV void osqp_shared_body(const DevFamily &F, const DevUpdate &U, const DevS
 #pragma unroll
             for (int g = 0; g < G; g++) {
                 if (I[g].done) continue;
+                // (an open instance's last verdict is "continue" (11) -- the register executor does not keep it live)
                 CheckOut o = co[g];
+                if (REG::active) { o.prim_res = 0; o.dual_res = 0; o.obj = 0; o.status = 11; }
                 double *wg = w + g * ldw;
                 ScaledNorms sn;
                 double rho_ws = F.rho;          // rho of the workspace this instance leaves behind

@@ -470,6 +470,52 @@ CPG_DEV void load_instance_coefficients(const DevRefactor &R, const double *Ml, 
         cf[t] = kind == 2u ? -(a * b) : (kind == 3u ? a : (kind == 1u ? 1.0 : 0.0));
     }
 }
+
+#ifdef CPG_GENI_NNZX
+// the merged program as the shared kernel's executor (osqp_shared_body<.., SharedRegExec>): every instance there has the
+// family's matrix and rho, so its coefficients come from ONE host-side factorisation (cpg_hip_set_shared_registers) and
+// are loaded once per wavefront; the offset / output-slot tables sit in LDS behind the base vectors.
+// CPG_SREG_LDS_REGS: the last coefficient registers are read from a block-shared LDS copy of the table, in the iteration
+// that uses them, instead of staying live -- next to the iterates, the termination test's state and the program's own
+// temporaries all 62 of MPC 12/4/10 did not fit 256 VGPRs, and the allocator spilled 17 of them to scratch, reloaded in
+// every iteration (codegen.SHARED_REG_LDS_REGS mirrors it)
+#ifndef CPG_SREG_LDS_REGS
+#define CPG_SREG_LDS_REGS 20
+#endif
+struct SharedRegExec {
+    static constexpr bool active = true;
+    static constexpr int nslots = CPG_GENI_NSLOTS + CPG_GEN_EXTRA_SLOTS;
+    static constexpr unsigned ncols = ((CPG_GENI_NSTEPS + 3u) / 4u) * 256u, nrows = ((CPG_GENI_NCHUNKS + 3u) / 4u) * 256u;
+    static constexpr int nlds = CPG_SREG_LDS_REGS < CPG_GENI_NREGS ? CPG_SREG_LDS_REGS : CPG_GENI_NREGS;
+    static constexpr int nreg = CPG_GENI_NREGS - nlds;
+    const double *gcf;
+    const unsigned short *gcols, *grows, *lc = nullptr, *lr = nullptr;
+    const double *lcf = nullptr;
+    double cf[nreg > 0 ? nreg : 1];
+    CPG_DEV explicit SharedRegExec(const DevShRegs &t) : gcf(t.cf), gcols(t.cols), grows(t.rows) {}
+    CPG_DEV size_t stage(double *lds) {          // (block-wide; the caller synchronises)
+        unsigned short *c = (unsigned short *)lds, *r = c + ncols;
+        double *v = lds + (ncols + nrows) / 4u;
+        const unsigned t0 = cpgw::thread_in_block(), nt = cpgw::block_threads();
+        for (unsigned t = t0; t < ncols; t += nt) c[t] = cpgw::gld(gcols, t);
+        for (unsigned t = t0; t < nrows; t += nt) r[t] = cpgw::gld(grows, t);
+        for (unsigned t = t0; t < 64u * (unsigned)nlds; t += nt) v[t] = cpgw::gld(gcf, 64u * (unsigned)nreg + t);
+        lc = c; lr = r; lcf = v;
+        return (ncols + nrows) / 4u + 64u * (unsigned)nlds;
+    }
+    CPG_DEV void load(int lane) {
+#pragma unroll
+        for (int t = 0; t < nreg; t++) cf[t] = cpgw::gld(gcf, (unsigned)t * 64u + (unsigned)lane);
+    }
+    // lane: the caller's per-iteration copy (cpgw::opaque) -- the LDS reads stay in the iteration
+    CPG_DEV void run(double *w, int lane) const {
+        double c[CPG_GENI_NREGS];
+#pragma unroll
+        for (int t = 0; t < CPG_GENI_NREGS; t++) c[t] = t < nreg ? cf[t < nreg ? t : 0] : lcf[(unsigned)(t - nreg) * 64u + (unsigned)lane];
+        run_program_inst(c, lc, lr, w, lane);
+    }
+};
+#endif
 #endif
 
 // GENI: the substitution runs through the generated instance executor (register-resident coefficients) instead of

@@ -136,7 +136,7 @@ class CpgLibrary:
 
     SYMBOLS = ['cpg_hip_device_count', 'cpg_hip_create_osqp', 'cpg_hip_create_clarabel', 'cpg_hip_destroy', 'cpg_hip_last_error',
                'cpg_hip_status_string', 'cpg_hip_set_default_settings', 'cpg_hip_set_setting',
-               'cpg_hip_get_setting', 'cpg_hip_set_build_option', 'cpg_hip_set_handover', 'cpg_hip_last_phase_ms', 'cpg_hip_set_update', 'cpg_hip_set_refactor', 'cpg_hip_set_refactor_merged', 'cpg_hip_set_resident', 'cpg_hip_set_gradient', 'cpg_hip_gradient_batch',
+               'cpg_hip_get_setting', 'cpg_hip_set_build_option', 'cpg_hip_set_handover', 'cpg_hip_last_phase_ms', 'cpg_hip_set_update', 'cpg_hip_set_refactor', 'cpg_hip_set_refactor_merged', 'cpg_hip_set_shared_registers', 'cpg_hip_set_resident', 'cpg_hip_set_gradient', 'cpg_hip_gradient_batch',
                'cpg_hip_solve_batch',
                'cpg_hip_solve_batch_device', 'cpg_hip_solve_batch_state', 'cpg_hip_solve_batch_device_state', 'cpg_hip_solve_batches_pipelined', 'cpg_hip_host_malloc',
                'cpg_hip_host_free', 'cpg_hip_synchronize', 'cpg_hip_get_stream', 'cpg_hip_last_kernel_ms',
@@ -168,6 +168,7 @@ class CpgLibrary:
         L.cpg_hip_set_refactor.argtypes = [C.c_void_p, C.POINTER(_Refactor)]
         L.cpg_hip_set_resident.argtypes = [C.c_void_p, C.POINTER(_Refactor), C.POINTER(_Resident)]
         L.cpg_hip_set_refactor_merged.argtypes = [C.c_void_p, C.POINTER(_Refactor), C.POINTER(_Resident)]
+        L.cpg_hip_set_shared_registers.argtypes = [C.c_void_p, C.POINTER(_Resident), _dp, C.c_int32, C.c_double, C.c_double]
         L.cpg_hip_set_gradient.argtypes = [C.c_void_p, C.POINTER(_Gradient)]
         L.cpg_hip_gradient_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp]
         L.cpg_hip_solve_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]
@@ -537,6 +538,8 @@ class BatchSolver:
         self._rg_key = None
         self._grad_loaded_on = set()
         self._hybrid = False
+        self._shared_cand = None           # refactor_plan.shared_mode_plan of this family (h_rs and the register executor)
+        self._sreg_done = False
         self.np_var = 0
         self._var_cols = np.zeros(0, dtype=np.int64)
 
@@ -575,7 +578,7 @@ class BatchSolver:
             rplan = None
             fps = _instance_fingerprints(self.lib.path)
             if fps:
-                cand = _rp.shared_mode_plan(Ps, As, o)
+                cand = self._shared_mode_candidate()
                 if cand.merged is not None and cand.merged.sol.fingerprint() in fps:
                     rplan = cand
                 elif cand.sol.fingerprint() in fps:
@@ -678,6 +681,46 @@ class BatchSolver:
             self.lib.check(self.lib.L.cpg_hip_set_launch(hh, *self._launch), 'set_launch')
         if getattr(self, '_placement', None) is not None:
             self.lib.check(self.lib.L.cpg_hip_set_program_placement(hh, self._placement), 'set_program_placement')
+
+    def _shared_mode_candidate(self):
+        if self._shared_cand is None:
+            from . import refactor_plan as _rp
+            o = self.plan.osqp_shared or self.plan.osqp
+            Ps, As = o.pruned(self.desc.P, self.desc.A)
+            self._shared_cand = _rp.shared_mode_plan(Ps, As, o)
+        return self._shared_cand
+
+    def _install_shared_registers(self) -> None:
+        """the shared kernel's register executor (cpg_hip_set_shared_registers): when this library's generated instance
+        executor runs the merged program of this family, that program's coefficients for the shared handle's factor --
+        the family's matrices, rho, sigma and row classes, canonical order -- computed once on the host.  Any other
+        library keeps the LDS-resident program."""
+        if self._sreg_done:
+            return
+        self._sreg_done = True
+        fps = _instance_fingerprints(self.lib.path)
+        if not fps:
+            return
+        mg = self._shared_mode_candidate().merged
+        if mg is None or mg.sol.fingerprint() not in fps:
+            return
+        from . import resident_plan as _rs
+        o = self.plan.osqp
+        rho, sigma = float(o.settings['rho']), float(o.settings['sigma'])
+        ct = self._family_ctype
+        # rho_vec as the kernel sets it from the row classes: equalities 1e3 rho, inequalities rho, free rows RHO_MIN
+        rho_vec = np.where(ct == 1, 1e3 * rho, np.where(ct == 0, rho, 1e-6))
+        Ps, As = (self.plan.osqp_shared or o).pruned(self.desc.P, self.desc.A)
+        fac = _rs.replay_factor(mg, Ps.data, As.data, sigma, 1.0 / rho_vec)
+        coef = np.ascontiguousarray(_rs.replay_solve_vals(mg, fac), dtype=np.float64)
+        ctab = np.ascontiguousarray(mg.sol.ctab, dtype=np.int32)
+        desc_ = np.ascontiguousarray(mg.sol.desc, dtype=np.uint32)
+        cols = np.ascontiguousarray(mg.sol.cols, dtype=np.uint16)
+        ms = _Resident(nnzX=mg.nnzX, sol_chunks=mg.sol.n_chunks, sol_nnz=mg.sol.nnz, sol_slots=mg.sol.n_slots,
+                       sol_ctab=ctab.ctypes.data_as(_ip), sol_desc=desc_.ctypes.data_as(C.POINTER(C.c_uint32)),
+                       sol_cols=cols.ctypes.data_as(_u16p))
+        self.lib.check(self.lib.L.cpg_hip_set_shared_registers(self.h_shared, C.byref(ms), _d(coef), len(coef), rho, sigma),
+                       'cpg_hip_set_shared_registers')
 
     def _apply_build_options(self, hh) -> None:
         for k, v in self.build_options.items():
@@ -826,7 +869,8 @@ class BatchSolver:
 
     def set_program_placement(self, in_lds: int = -1):
         """-1 automatic, 0 stream the solve program from L2/HBM, 1 keep it resident in LDS, 2 (per-instance factor
-        handles) the streaming executor with its entry words in LDS instead of a generated executor"""
+        handles) the streaming executor with its entry words in LDS instead of a generated executor, 3 the squad executor,
+        4 the register executor of the shared kernel (include/cpg_hip.h)"""
         self._placement = in_lds
         for hh in (self.h_shared, self.h_ref, self.h_rs):
             if hh is not None and hh.value:
@@ -902,6 +946,7 @@ class BatchSolver:
                       map_q=_csr_struct(Mq, keep), map_u=_csr_struct(Mu, keep),
                       map_d=_csr_struct(Md, keep))
         self.lib.check(self.lib.L.cpg_hip_set_update(self.h, C.byref(upd)), 'cpg_hip_set_update')
+        self._install_shared_registers()
         if hybrid:
             # rho adaptation: instances whose rho changes continue on their own factor of the SAME matrices
             self._set_refactor(cols, th_fixed, q_setup, shared_mats=True)

@@ -334,6 +334,16 @@ int cpg_hip_set_refactor(cpg_handle_t h, const cpg_osqp_refactor_t *rf);
  * cpg_hip_get_setting(h, "generated_instance_executor") reports which. */
 int cpg_hip_set_refactor_merged(cpg_handle_t h, const cpg_osqp_refactor_t *rf, const cpg_osqp_resident_t *mg);
 
+/* Register executor of a SHARED-factor handle: when this library's generated instance executor runs the merged program
+ * mg (its sol_* fields; the header's fingerprint decides), the shared kernel can run that program too, with the
+ * coefficients of the family's factor in registers.  coef: [n_coef = mg->sol_nnz] the program's coefficient per entry
+ * (entry order) for the KKT matrix at rho / sigma (cvxpygen_amd.resident_plan.replay_factor / replay_solve_vals).  A solve
+ * uses the table only while the handle's rho and sigma are the ones given here; otherwise, and for any other library,
+ * the LDS-resident program runs (CPG_OK, nothing installed).  Placement -1 picks it where it is usable, 4 forces it;
+ * cpg_hip_get_setting(h, "register_executor") reports whether a solve would run it. */
+int cpg_hip_set_shared_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, const double *coef, int32_t n_coef,
+                                 double rho, double sigma);
+
 /* cpg_hip_set_refactor(h, rf), and -- when this library carries the generated resident executor of exactly this
  * family (cvxpygen_amd.codegen.resident_header; the merged program's fingerprint decides) -- the resident kernel's
  * tables: solves then run cpg_osqp_resident.h instead of the streaming kernel.  cpg_hip_get_setting(h,
@@ -403,7 +413,9 @@ int cpg_hip_set_launch(cpg_handle_t h, int waves_per_block, int inst_per_wave, i
  * 3 = shared-factor handles of a family library that carries the squad executor (cvxpygen_amd.codegen.squad_header;
  * cpg_hip_get_setting(h, "squad_executor") reports 1.0 once selected): the solve program in the REGISTERS of a workgroup of
  * four wavefronts that solves four instances at a time (csrc/cpg_osqp_squad.h) -- same results; measured slower than 1 on
- * MI355X, kept selectable for comparison; a solve fails with CPG_E_UNSUPPORTED where the library has none.
+ * MI355X, kept selectable for comparison; a solve fails with CPG_E_UNSUPPORTED where the library has none;
+ * 4 = shared-factor handles: the register executor (cpg_hip_set_shared_registers), which -1 also picks where it is usable;
+ * a solve fails with CPG_E_UNSUPPORTED where it is not.  Per-instance factor handles take 4 as they take 3.
  * Replaces nothing of the reference's interface: the generated C has one placement, the CPU's (cvxpygen/solvers/osqp.py:62). */
 int cpg_hip_set_program_placement(cpg_handle_t h, int in_lds);
 
