@@ -72,7 +72,8 @@ struct cpg_solver_s {
     cpg::DevSettings S{};
     int waves_per_block = 0, inst_per_wave = 1, blocks_per_cu = 0;
     int program_in_lds = -1;            // -1 auto, 0 stream from L2/HBM, 1 resident in LDS, 3 squad executor (program in registers),
-                                        // 4 register executor (merged instance program, family coefficients in registers)
+                                        // 4 register executor (merged instance program, family coefficients in registers),
+                                        // 5 single-kernel step (the linked handle's instance kernel serves the whole batch)
     bool squad_ok = false;              // family library with this family's squad executor (cpg_osqp_squad.h)
     // register executor of the shared kernel (cpg_hip_set_shared_registers): its device tables, and the rho / sigma its
     // coefficients were computed at -- a solve uses them only while F.rho / F.sigma are still those
@@ -80,6 +81,9 @@ struct cpg_solver_s {
     bool sreg_ok = false;
     double sreg_rho = 0.0, sreg_sigma = 0.0;
     std::vector<void *> sreg_owned;
+    // family coefficients of the generated instance executor on a per-instance factor handle (cpg_hip_set_instance_registers):
+    // the table R.fam_cf / R.fam_ct is stamped with the rho / sigma it was computed at (R.fam_rho / R.fam_sigma)
+    std::vector<void *> ireg_owned;
     int num_cu = 256;
     size_t lds_limit = 160 * 1024;
     unsigned *d_counter = nullptr;
@@ -102,10 +106,12 @@ struct cpg_solver_s {
     // hybrid execution of rho adaptation (cpg_hip_set_handover): instances of this shared-factor handle whose
     // rho changes continue on `linked`'s per-instance factor kernel, launched behind on this handle's stream
     cpg_solver_s *linked = nullptr;
+    std::vector<cpg_solver_s *> linked_from;   // (on the per-instance handle) the shared-factor handles that link to it: their solves launch ITS kernel on THEIR streams
     bool flag_rho_changes = false;    // build option: a solve WITHOUT a linked handle may flag rho changes as status -2 instead of refusing
     DevBuf ho_state, ho_list;
     rt_event_t ev_mid{};
     bool two_phase_last = false;
+    bool single_last = false;           // the last solve ran the single-kernel step (d_counter[1]: instances that refactored in the loop)
 };
 
 // ---- runtime primitives -------------------------------------------------------------------------
@@ -131,6 +137,14 @@ static int rt_d2h(cpg_handle_t h, void *dst, const void *src, size_t bytes) {
 static int rt_sync(cpg_handle_t h) {
     RT_CHECK(hipStreamSynchronize(h->stream));
     return CPG_OK;
+}
+// the handle's own stream and the streams of the shared-factor handles linked to it (cpg_hip_set_handover): their solves read this
+// handle's tables, so nothing of them may be freed before those streams are idle too
+static int rt_sync_linked(cpg_handle_t h) {
+    int rc = rt_sync(h);
+    for (cpg_solver_s *s : h->linked_from)
+        if (!rc) rc = rt_sync(s);
+    return rc;
 }
 static int rt_set_device(int dev) {
     RT_CHECK(hipSetDevice(dev));
@@ -550,6 +564,27 @@ static cpg::DevBatch make_batch(int64_t B, const double *d_theta, const double *
     return Bt;
 }
 
+#ifdef CPG_GENI_HEADER
+// dynamic LDS of the generated instance kernel's launch (eight wavefronts per workgroup): the executor's tables, then per wavefront
+// the work vector | q | u -- or the factor (+ a zero slot) while it is computed.  launch_per_instance runs that kernel when
+// instance_kernel_fits; the single-kernel step of a linked shared-factor handle is offered on the same condition.
+static size_t instance_kernel_lds(const cpg_solver_s *h) {
+    const size_t tab = (size_t)(((CPG_GENI_NSTEPS + 3) / 4) * 256 + ((CPG_GENI_NCHUNKS + 3) / 4) * 256) * sizeof(unsigned short);
+    const size_t nq = (size_t)(h->F.n + h->F.m);
+    size_t per_wave = (size_t)(CPG_GENI_NSLOTS + CPG_GEN_EXTRA_SLOTS) + nq + (nq & 1);
+#ifdef CPG_GENI_FAC_NSTEPS
+    const size_t fac = (size_t)CPG_GENI_FAC_ZERO + 1;
+#else
+    const size_t fac = (size_t)h->R.nnzL + nq;
+#endif
+    if (per_wave < fac) per_wave = fac + (fac & 1);
+    return tab + 8 * per_wave * sizeof(double);
+}
+static bool instance_kernel_fits(const cpg_solver_s *h) {
+    return h->R.gi_ok && h->program_in_lds != 0 && h->program_in_lds != 2 && instance_kernel_lds(h) <= h->lds_limit;
+}
+#endif
+
 // per-instance factor kernel of handle `h` (its tables, its scratch) on `stream` with settings `S`
 static int launch_per_instance(cpg_handle_t h, rt_stream_t stream, const cpg::DevSettings &S, cpg::DevBatch &Bt) {
     int rc;
@@ -597,25 +632,14 @@ static int launch_per_instance(cpg_handle_t h, rt_stream_t stream, const cpg::De
     }
 #endif
 #ifdef CPG_GENI_HEADER
-    if (h->R.gi_ok && h->program_in_lds != 0 && h->program_in_lds != 2) {
+    if (instance_kernel_fits(h)) {
         const int W = 8;                               // one workgroup of eight wavefronts per CU shares the tables       // generated instance executor (cpg_hip_set_program_placement(0): the streaming one)
-        const size_t tab = (size_t)(((CPG_GENI_NSTEPS + 3) / 4) * 256 + ((CPG_GENI_NCHUNKS + 3) / 4) * 256) * sizeof(unsigned short);
-        const size_t nq = (size_t)(h->F.n + h->F.m);
-        size_t per_wave = (size_t)(CPG_GENI_NSLOTS + CPG_GEN_EXTRA_SLOTS) + nq + (nq & 1);   // work vector | q | u ...
-#ifdef CPG_GENI_FAC_NSTEPS
-        const size_t fac = (size_t)CPG_GENI_FAC_ZERO + 1;                                     // ... or the factor (+ a zero slot) while it is computed
-#else
-        const size_t fac = (size_t)h->R.nnzL + nq;                                            // ... or the factor while it is computed
-#endif
-        if (per_wave < fac) per_wave = fac + (fac & 1);
-        const size_t lds = tab + (size_t)W * per_wave * sizeof(double);
-        if (lds <= h->lds_limit) {
-            const int blocks = grid_blocks(h, Bt.B, W, 1);   // 8 wavefronts per CU: the register budget of the kernel
-            if ((rc = scratch(blocks, W, h->R.buf_doubles))) return rc;
-            if (slot_class(h, rc, [&](auto NSX, auto NSZ) {
-                    return launch_kernel(osqp_instance_kernel<NSX, NSZ>, blocks, W * 64, lds, stream, h->F, h->R, S, Bt); }))
-                return rc;
-        }
+        const size_t lds = instance_kernel_lds(h);
+        const int blocks = grid_blocks(h, Bt.B, W, 1);   // 8 wavefronts per CU: the register budget of the kernel
+        if ((rc = scratch(blocks, W, h->R.buf_doubles))) return rc;
+        if (slot_class(h, rc, [&](auto NSX, auto NSZ) {
+                return launch_kernel(osqp_instance_kernel<NSX, NSZ>, blocks, W * 64, lds, stream, h->F, h->R, S, Bt); }))
+            return rc;
     }
 #endif
 #ifdef CPG_REFACTOR_CR_LDS
@@ -733,6 +757,33 @@ static int shared_launches(cpg_handle_t h, cpg::DevBatch &Bt, bool two_phase, La
     return end_solve(h);
 }
 
+// Single-kernel step of a shared-factor handle with rho adaptation: the linked handle's generated instance kernel (merged
+// program) serves the WHOLE batch from iteration 0 -- it starts every instance from the family's coefficient table
+// (cpg_hip_set_instance_registers) instead of factoring, and refactors in its loop when an instance's rho changes.  Usable
+// while that table is installed for the rho / sigma both handles hold now and the linked handle launches that kernel.
+static bool single_kernel_usable(cpg_handle_t h) {
+#if defined(CPG_GENI_HEADER) && defined(CPG_GENI_NNZX)
+    const cpg_solver_s *l = h->linked;
+    return !h->refactor_mode && !h->conic && l && l->refactor_mode && instance_kernel_fits(l) && l->R.shared_mats && l->R.fam_cf &&
+           l->R.fam_rho == l->F.rho && l->R.fam_sigma == l->F.sigma &&
+           h->F.rho == l->F.rho && h->F.sigma == l->F.sigma && h->F.alpha == l->F.alpha;
+#else
+    (void)h;
+    return false;
+#endif
+}
+static bool single_kernel_selected(cpg_handle_t h) {
+    return (h->program_in_lds == -1 || h->program_in_lds == 5) && h->S.adaptive_rho && h->S.adaptive_rho_interval > 0 && single_kernel_usable(h);
+}
+static int solve_single_kernel(cpg_handle_t h, cpg::DevBatch &Bt) {
+    int rc;
+    cpg::DevBatch B1 = Bt;
+    B1.counter = h->d_counter; B1.ho_count = h->d_counter + 1;      // (ho_list / ho_state stay null: nothing is handed over)
+    if ((rc = begin_solve(h)) || (rc = launch_per_instance(h->linked, h->stream, h->S, B1))) return rc;
+    h->two_phase_last = false; h->single_last = true;
+    return end_solve(h);
+}
+
 // OSQP handle with the shared factor
 static int solve_shared(cpg_handle_t h, cpg::DevBatch &Bt) {
     // rho adaptation on the shared factor: hybrid execution when a per-instance factor handle is linked
@@ -748,6 +799,14 @@ static int solve_shared(cpg_handle_t h, cpg::DevBatch &Bt) {
         return CPG_E_UNSUPPORTED;
     }
     if (two_phase && !h->linked->refactor_mode) { set_error("linked handle has no per-instance factor tables (cpg_hip_set_refactor)"); return CPG_E_BADARG; }
+    h->single_last = false;
+    if (two_phase && single_kernel_selected(h)) return solve_single_kernel(h, Bt);
+    if (two_phase && h->program_in_lds == 5) {
+        set_error("no single-kernel step for this handle (cpg_hip_set_program_placement(5)): the library carries no merged instance "
+                  "program of the family, cpg_hip_set_instance_registers was not called on the linked handle for its rho / sigma, or "
+                  "the linked handle was told to stream");
+        return CPG_E_UNSUPPORTED;
+    }
     const int G = h->inst_per_wave;
     const size_t N = (size_t)(h->F.n + h->F.m);
 #ifdef CPG_GENQ_HEADER
@@ -765,7 +824,7 @@ static int solve_shared(cpg_handle_t h, cpg::DevBatch &Bt) {
     }
 #endif
     if (h->program_in_lds == 3) { set_error("this library carries no squad executor for the family (cpg_hip_set_program_placement(3))"); return CPG_E_UNSUPPORTED; }
-    if (h->program_in_lds == -1 || h->program_in_lds == 4) {
+    if (h->program_in_lds == -1 || h->program_in_lds == 4 || h->program_in_lds == 5) {      // (5 without rho adaptation: as -1)
 #if defined(CPG_GENI_HEADER) && defined(CPG_GENI_NNZX)
         if (shared_reg_usable(h)) {
             // register executor: the merged program, the family's coefficients in registers; one workgroup per CU
@@ -814,7 +873,7 @@ static int solve_shared(cpg_handle_t h, cpg::DevBatch &Bt) {
     // table-driven kernels, automatic placement: the streaming executor (program through L2, operands
     // of eight steps in flight, more resident waves) beats the LDS-resident table walk -- 1.44 M vs
     // 1.10 M instances/s on MPC 12/4/10; the LDS-resident form remains for G = 2 and on request
-    const int placement = h->program_in_lds == 2 ? -1 : h->program_in_lds;     // (2 concerns per-instance factor handles only)
+    const int placement = h->program_in_lds == 2 || h->program_in_lds == 5 ? -1 : h->program_in_lds;     // (2 concerns per-instance factor handles only)
 #ifdef CPG_GEN_HEADER
     const bool prefer_stream = false;   // family library: the generated executor works on the LDS-resident program
 #else
@@ -1029,7 +1088,9 @@ int cpg_hip_get_setting(cpg_handle_t h, const char *name, double *v) {
     else if (s == "adaptive_rho_tolerance") *v = h->S.adaptive_rho_tolerance;
     else if (s == "check_dualgap") *v = h->S.check_dualgap;
     // (read-only facts about the handle) 1: per-instance solves of this handle run the generated instance executor
-    else if (s == "register_executor") *v = (h->program_in_lds == -1 || h->program_in_lds == 4) && shared_reg_usable(h) ? 1.0 : 0.0;
+    else if (s == "register_executor") *v = (h->program_in_lds == -1 || h->program_in_lds == 4 || h->program_in_lds == 5) && shared_reg_usable(h) ? 1.0 : 0.0;
+    // ... 1: a solve of this shared-factor handle runs the single-kernel step (the linked handle's instance kernel on the whole batch)
+    else if (s == "single_kernel_step") *v = single_kernel_selected(h) ? 1.0 : 0.0;
     else if (s == "squad_executor") *v = (!h->refactor_mode && !h->conic && h->squad_ok && h->program_in_lds == 3 && h->inst_per_wave == 1) ? 1.0 : 0.0;
     else if (s == "team_executor") {
         // wavefronts per instance of the team kernel this handle's per-instance solves run on; 0: another kernel (no team plan, the
@@ -1539,8 +1600,11 @@ static void free_list(std::vector<void *> &v) { for (void *p : v) rt_free(p); v.
 int cpg_hip_destroy(cpg_handle_t h) {
     if (!h) return CPG_OK;
     rt_set_device(h->device);
-    rt_sync(h);
-    free_list(h->owned); free_list(h->update_owned); free_list(h->refactor_owned); free_list(h->sreg_owned); free_list(h->resident_owned); free_list(h->gradient_owned);
+    rt_sync_linked(h);
+    // (links in both directions end here: neither side keeps a pointer to a destroyed handle)
+    if (h->linked) h->linked->linked_from.erase(std::remove(h->linked->linked_from.begin(), h->linked->linked_from.end(), h), h->linked->linked_from.end());
+    for (cpg_solver_s *s : h->linked_from) s->linked = nullptr;
+    free_list(h->owned); free_list(h->update_owned); free_list(h->refactor_owned); free_list(h->sreg_owned); free_list(h->ireg_owned); free_list(h->resident_owned); free_list(h->gradient_owned);
     free_buf(h->g_theta); free_buf(h->g_x); free_buf(h->g_y); free_buf(h->g_dprim); free_buf(h->g_dtheta);
     if (h->d_counter) rt_free(h->d_counter);
     free_buf(h->scratch);
@@ -1760,11 +1824,13 @@ int cpg_hip_set_refactor(cpg_handle_t h, const cpg_osqp_refactor_t *r) {
     if (!h || !r) { set_error("null argument"); return CPG_E_BADARG; }
     int rc = rt_set_device(h->device);
     if (rc) return rc;
-    if ((rc = rt_sync(h))) return rc;
+    if ((rc = rt_sync_linked(h))) return rc;
     free_list(h->refactor_owned);
     free_list(h->resident_owned); h->Rs = cpg::DevResident{};      // (cpg_hip_set_resident installs its tables behind this call)
+    free_list(h->ireg_owned);                                      // (cpg_hip_set_instance_registers likewise)
     std::vector<void *> &own = h->refactor_owned;
     cpg::DevRefactor &R = h->R;
+    R.fam_cf = nullptr; R.fam_ct = nullptr; R.fam_rho = 0.0; R.fam_sigma = 0.0;
     const size_t n = h->F.n, m = h->F.m, N = n + m;
     R.nnzP = r->nnzP; R.nnzA = r->nnzA; R.nnzL = r->nnzL; R.n_eq = h->F.n_eq; R.np_var = r->np_var;
     R.scaling_iters = r->scaling_iters; R.d_base = r->d_base;
@@ -1897,6 +1963,58 @@ int cpg_hip_set_refactor_merged(cpg_handle_t h, const cpg_osqp_refactor_t *r, co
     return CPG_OK;
 }
 
+#if defined(CPG_GENI_HEADER) && defined(CPG_GENI_NNZX)
+// the merged program's coefficients (entry order) per (register, lane), laid out as load_instance_coefficients fills cf: idle
+// lanes hold 0.0; false: two steps claim one lane of a register
+static bool pack_register_coefficients(const double *coef, std::vector<double> &cf) {
+    static const int steps[][4] = CPG_GENI_STEPS;                 // {first entry, active lanes, coefficient register, lane shift}
+    cf.assign((size_t)CPG_GENI_NREGS * 64, 0.0);
+    std::vector<char> taken(cf.size(), 0);
+    for (int t = 0; t < CPG_GENI_NSTEPS; t++) {
+        const int e = steps[t][0], cnt = steps[t][1], reg = steps[t][2], sh = steps[t][3];
+        if (reg < 0 || reg >= CPG_GENI_NREGS) return false;
+        for (int l = 0; l < cnt; l++) {
+            const size_t at = (size_t)reg * 64 + (size_t)(l + sh);
+            if (taken[at]) return false;
+            taken[at] = 1;
+            cf[at] = coef[e + l];
+        }
+    }
+    return true;
+}
+#endif
+
+int cpg_hip_set_instance_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, const double *coef, int32_t n_coef,
+                                   const int8_t *row_class, double rho, double sigma) {
+    if (h && h->conic) { set_error("not available for a conic (interior-point) handle"); return CPG_E_BADARG; }
+    if (!h || !mg || !coef || !row_class) { set_error("null argument"); return CPG_E_BADARG; }
+    if (!h->refactor_mode || !h->R.shared_mats) { set_error("cpg_hip_set_instance_registers: needs a per-instance factor handle in shared-matrix mode"); return CPG_E_BADARG; }
+    int rc = rt_sync_linked(h);                                   // (a solve in flight, also one of a linking shared-factor handle, may still read the old table)
+    if (rc) return rc;
+    h->R.fam_cf = nullptr; h->R.fam_ct = nullptr; h->R.fam_rho = 0.0; h->R.fam_sigma = 0.0;
+    free_list(h->ireg_owned);
+#if defined(CPG_GENI_HEADER) && defined(CPG_GENI_NNZX)
+    // (the handle runs the merged program of this library -- cpg_hip_set_refactor_merged checked its fingerprint -- and mg is that program)
+    if (!(h->R.gi_ok && mg->nnzX == CPG_GENI_NNZX && mg->sol_chunks == CPG_GENI_NCHUNKS && mg->sol_nnz == CPG_GENI_NNZ &&
+          mg->sol_slots == CPG_GENI_NSLOTS && n_coef == mg->sol_nnz))
+        return CPG_OK;
+    if (program_fingerprint(mg->sol_ctab, mg->sol_desc, mg->sol_cols, mg->sol_chunks, mg->sol_nnz) != CPG_GENI_FINGERPRINT) return CPG_OK;
+    std::vector<double> cf;
+    if (!pack_register_coefficients(coef, cf)) return CPG_OK;
+    for (int i = 0; i < h->F.m; i++)                              // (the kernel's own classes: equalities first, then 0 or -1)
+        if (row_class[i] != (i < h->F.n_eq ? 1 : row_class[i] == -1 ? -1 : 0)) { set_error("cpg_hip_set_instance_registers: row classes"); return CPG_E_BADARG; }
+    const double *d_cf = nullptr;
+    const signed char *d_ct = nullptr;
+    if ((rc = upload<double>(h, h->ireg_owned, cf.data(), cf.size(), &d_cf))) return rc;
+    if ((rc = upload<signed char>(h, h->ireg_owned, (const signed char *)row_class, (size_t)h->F.m, &d_ct))) return rc;
+    if ((rc = rt_sync(h))) return rc;                             // (the host vector above ends here)
+    h->R.fam_cf = d_cf; h->R.fam_ct = d_ct; h->R.fam_rho = rho; h->R.fam_sigma = sigma;
+#else
+    (void)n_coef; (void)rho; (void)sigma;
+#endif
+    return CPG_OK;
+}
+
 int cpg_hip_set_shared_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, const double *coef, int32_t n_coef, double rho, double sigma) {
     if (h && h->conic) { set_error("not available for a conic (interior-point) handle"); return CPG_E_BADARG; }
     if (!h || !mg || !coef) { set_error("null argument"); return CPG_E_BADARG; }
@@ -1922,19 +2040,8 @@ int cpg_hip_set_shared_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, 
     if (!generated_tables(mg->sol_ctab, mg->sol_desc, mg->sol_cols, mg->sol_chunks, mg->sol_nnz, mg->sol_slots, steps, CPG_GENI_NSTEPS,
                           gcols, grows, chunk_shift))
         return CPG_OK;
-    // the coefficient of every (register, lane), laid out as load_instance_coefficients fills cf: idle lanes hold 0.0
-    std::vector<double> cf((size_t)CPG_GENI_NREGS * 64, 0.0);
-    std::vector<char> taken(cf.size(), 0);
-    for (int t = 0; t < CPG_GENI_NSTEPS; t++) {
-        const int e = steps[t][0], cnt = steps[t][1], reg = steps[t][2], sh = steps[t][3];
-        if (reg < 0 || reg >= CPG_GENI_NREGS) return CPG_OK;
-        for (int l = 0; l < cnt; l++) {
-            const size_t at = (size_t)reg * 64 + (size_t)(l + sh);
-            if (taken[at]) return CPG_OK;                         // (two steps on one lane of a register)
-            taken[at] = 1;
-            cf[at] = coef[e + l];
-        }
-    }
+    std::vector<double> cf;
+    if (!pack_register_coefficients(coef, cf)) return CPG_OK;
     cpg::DevShRegs T{};
     if ((rc = upload<double>(h, h->sreg_owned, cf.data(), cf.size(), &T.cf))) return rc;
     if ((rc = upload<unsigned short>(h, h->sreg_owned, gcols.data(), gcols.size(), &T.cols))) return rc;
@@ -2454,7 +2561,10 @@ int cpg_hip_set_handover(cpg_handle_t h, cpg_handle_t per_instance) {
     if (per_instance && (per_instance->device != h->device || per_instance->F.n != h->F.n || per_instance->F.m != h->F.m ||
                          per_instance->F.n_prim != h->F.n_prim || per_instance->F.n_dual != h->F.n_dual)) {
         set_error("cpg_hip_set_handover: the two handles must describe the same family on the same device"); return CPG_E_BADARG; }
+    auto unlink = [&](cpg_solver_s *l) { if (l) l->linked_from.erase(std::remove(l->linked_from.begin(), l->linked_from.end(), h), l->linked_from.end()); };
+    unlink(h->linked);
     h->linked = per_instance;
+    if (per_instance) per_instance->linked_from.push_back(h);
     return CPG_OK;
 }
 
@@ -2462,7 +2572,16 @@ int cpg_hip_last_phase_ms(cpg_handle_t h, float *ms_shared, float *ms_per_instan
     if (!h || !ms_shared || !ms_per_instance || !n_handed_over) { set_error("null argument"); return CPG_E_BADARG; }
     RT_CHECK(hipEventSynchronize(h->ev1));
     *ms_per_instance = 0.f; *n_handed_over = 0;
-    if (!h->two_phase_last) { RT_CHECK(hipEventElapsedTime(ms_shared, h->ev0, h->ev1)); return CPG_OK; }
+    if (!h->two_phase_last) {
+        RT_CHECK(hipEventElapsedTime(ms_shared, h->ev0, h->ev1));
+        if (h->single_last) {     // single-kernel step: one phase; the count is of the instances that refactored in its loop
+            unsigned cnt = 0;
+            RT_CHECK(hipMemcpyAsync(&cnt, h->d_counter + 1, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+            RT_CHECK(hipStreamSynchronize(h->stream));
+            *n_handed_over = (int64_t)cnt;
+        }
+        return CPG_OK;
+    }
     RT_CHECK(hipEventElapsedTime(ms_shared, h->ev0, h->ev_mid));
     RT_CHECK(hipEventElapsedTime(ms_per_instance, h->ev_mid, h->ev1));
     unsigned cnt = 0;
@@ -2549,7 +2668,7 @@ int cpg_hip_set_launch(cpg_handle_t h, int waves_per_block, int inst_per_wave, i
 }
 
 int cpg_hip_set_program_placement(cpg_handle_t h, int in_lds) {
-    if (!h || in_lds < -1 || in_lds > 4) { set_error("in_lds must be -1, 0, 1, 2, 3 or 4"); return CPG_E_BADARG; }
+    if (!h || in_lds < -1 || in_lds > 5) { set_error("in_lds must be -1, 0, 1, 2, 3, 4 or 5"); return CPG_E_BADARG; }
     h->program_in_lds = in_lds;
     return CPG_OK;
 }

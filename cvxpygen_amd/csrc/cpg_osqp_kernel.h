@@ -119,6 +119,9 @@ struct DevSettings {
     double adaptive_rho_tolerance;
     int warm_starting;            // 1: start from DevBatch::state_in when it is given
     int debug_stage;              // measurements only (0 = off): the per-instance factor kernel leaves an instance after stage k of its set-up
+                                  // (1 - 3); generated instance kernel: 20 = time stamps of the instance's stages over its first primal
+                                  // results, 21 (tests) = coefficient register b mod NREGS of instance b over its first 64 primal results
+                                  // (nothing where the family has fewer than 64)
 };
 struct DevBatch {
     long long B;

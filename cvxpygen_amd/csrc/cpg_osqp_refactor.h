@@ -108,6 +108,13 @@ struct DevRefactor {
     const double *fac_kc_cl;            // the same per (chunk, lane) of the factorisation schedule (no detour over the task number)
     const int *fac_krow_cl;
     const int *fac_kind_cl, *fac_idx_cl;   // per (chunk, lane): KKT source of the destination (per-instance matrices)
+    // Family coefficients of the generated instance executor (cpg_hip_set_instance_registers, merged program): per
+    // (register, lane) what load_instance_coefficients leaves in cf after a factorisation at rho = fam_rho, sigma = fam_sigma
+    // with the row classes fam_ct [m] -- computed once on the host.  An instance whose workspace rho, sigma and row classes
+    // are exactly these starts from the table instead of factoring; null: none installed.
+    const double *fam_cf;
+    const signed char *fam_ct;
+    double fam_rho, fam_sigma;
 };
 
 #define CPG_K_NONE 0
@@ -638,15 +645,51 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
         int n_ts = 0;
 #define CPG_INST_PROBE() do { if (GENI && probe && n_ts < 8) ts[n_ts++] = cpgw::clock100(); } while (0)
         CPG_INST_PROBE();
+#ifdef CPG_GENI_HEADER
+        // generated instance kernel: an instance that starts at the family's rho and sigma needs no factorisation of its own when
+        // its rows also have the family's classes (tested below, once u is known) -- its coefficients are the family's table.
+        // The family's classes are requested here, with the canonicalisation's loads; the table itself where it is used (every
+        // instance reloads it, an adapt_rho overwrites cf): requested up here its 2 x NREGS registers were live across the
+        // whole set-up and went through scratch (1 696 instead of 608 bytes per lane)
+        double cf[CPG_GENI_NREGS];           // (dead, hence free, in the streaming instantiation)
+        signed char fct[NSZ];
+#pragma unroll
+        for (int s = 0; s < NSZ; s++) fct[s] = 0;
+        const bool fam_start = GENI && R.fam_cf != nullptr && rho == R.fam_rho && F0.sigma == R.fam_sigma;     // (uniform)
+        if (GENI && fam_start) {
+            const unsigned ln = (unsigned)cpgw::opaque(lane);      // (addresses local to this block, see load_instance_coefficients)
+#pragma unroll
+            for (int s = 0; s < NSZ; s++) { const unsigned i = ln + 64u * (unsigned)s; fct[s] = i < m ? cpgw::gld(R.fam_ct, i) : (signed char)0; }
+        }
+#endif
         // ---- 1. canonicalise (unscaled; scaled in shared-matrix mode): P, A values, q, u, d
         if (!shared) {
             for (unsigned k = (unsigned)lane; k < (unsigned)R.nnzA; k += 64u) cpgw::gst(B.A, k, csr_row(R.map_A, k, theta, cpgw::gld(R.A_base, k)));
             for (unsigned k = (unsigned)lane; k < (unsigned)R.nnzP; k += 64u) cpgw::gst(B.P, k, csr_row(R.map_P, k, theta, cpgw::gld(R.P_base, k)));
         }
-        for (unsigned i = (unsigned)lane; i < n; i += 64u) cpgw::gst(B.q, i, csr_row(R.map_q, i, theta, cpgw::gld(R.q_base, i)));
-        for (unsigned i = (unsigned)lane; i < m; i += 64u) cpgw::gst(B.u, i, csr_row(R.map_u, i, theta, cpgw::gld(R.u_base, i)));
+        // (generated instance kernel: q and u stay in registers for the row classes and the LDS copies below; the global copies
+        // serve a later factor_in_lds, which orders them itself -- nothing here waits for them)
+        double qv[GENI ? NSX : 1], uv[GENI ? NSZ : 1];
+        if (GENI) {
+            const unsigned ln = (unsigned)cpgw::opaque(lane);
+#pragma unroll
+            for (int s = 0; s < NSX; s++) {
+                const unsigned i = ln + 64u * (unsigned)s;
+                qv[GENI ? s : 0] = 0.0;
+                if ((unsigned)lane + 64u * (unsigned)s < n) { qv[GENI ? s : 0] = csr_row(R.map_q, i, theta, cpgw::gld(R.q_base, i)); cpgw::gst(B.q, i, qv[GENI ? s : 0]); }
+            }
+#pragma unroll
+            for (int s = 0; s < NSZ; s++) {
+                const unsigned i = ln + 64u * (unsigned)s;
+                uv[GENI ? s : 0] = 0.0;
+                if ((unsigned)lane + 64u * (unsigned)s < m) { uv[GENI ? s : 0] = csr_row(R.map_u, i, theta, cpgw::gld(R.u_base, i)); cpgw::gst(B.u, i, uv[GENI ? s : 0]); }
+            }
+        } else {
+            for (unsigned i = (unsigned)lane; i < n; i += 64u) cpgw::gst(B.q, i, csr_row(R.map_q, i, theta, cpgw::gld(R.q_base, i)));
+            for (unsigned i = (unsigned)lane; i < m; i += 64u) cpgw::gst(B.u, i, csr_row(R.map_u, i, theta, cpgw::gld(R.u_base, i)));
+        }
         const double dconst = csr_row(R.map_d, 0, theta, R.d_base);
-        cpgw::mem_order();
+        if (!GENI) cpgw::mem_order();
         double cs = shared ? R.cs : 1.0;
         if (!shared) {
 #ifdef CPG_REFACTOR_ROW_COPY
@@ -735,7 +778,7 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
             const unsigned ic = (unsigned)lane + 64u * (unsigned)s;           // tests (range known: they fold on full slots when m, n_eq are constants)
             ct[s] = 0;
             if (ic < m) {
-                double uu = cpgw::gld((const double *)B.u, i);      // shared-matrix mode: already E u
+                double uu = GENI ? uv[GENI ? s : 0] : cpgw::gld((const double *)B.u, i);      // shared-matrix mode: already E u
                 if (!shared) {
                     const double ei = w[n + i];
                     uu = ei * uu;
@@ -746,8 +789,7 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
                 cpgw::gst(B.rinv, i, ct[s] == 1 ? ri_eq : (ct[s] == 0 ? ri_in : ri_fr));
             }
         }
-        cpgw::lds_order();
-        cpgw::mem_order();
+        if (!GENI) { cpgw::lds_order(); cpgw::mem_order(); }        // (factor_in_lds orders B.rinv itself)
         // generated instance kernel: the step sizes of the slots whose class is not a compile-time fact (a slot below n_eq is
         // all equalities) as per-lane values, set here and after an adapt_rho -- the ADMM loop then selects nothing
         double rvv[NSZ], riv[NSZ];
@@ -775,7 +817,6 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
             }
         };
 #ifdef CPG_GENI_HEADER
-        double cf[CPG_GENI_NREGS];           // (dead, hence free, in the streaming instantiation)
         auto factor_in_lds = [&]() __attribute__((always_inline)) {
             cpgw::mem_order();                // B.rinv
 #ifdef CPG_GENI_FAC_NSTEPS
@@ -801,11 +842,42 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
         };
         if (__builtin_expect(S.debug_stage == 2, 0)) { if (lane == 0) { Bt.status[b] = 11; Bt.iter[b] = 0; } continue; }     // (row classes, rho_vec)
         CPG_INST_PROBE();          // 1: canonicalised, row classes
-        if (GENI) factor_in_lds();
+        if (GENI) {
+            // the family's table serves when every row has the family's class as well (a row in another class has another
+            // 1 / rho_vec on the KKT diagonal): a wave-wide vote; then only the slice preparation of factor_in_lds remains,
+            // with q and u written from registers
+            bool other = false;
+#pragma unroll
+            for (int s = 0; s < NSZ; s++) other = other || ((unsigned)lane + 64u * (unsigned)s < m && ct[s] != fct[s]);
+            if (fam_start && cpgw::ballot(other) == 0ull) {
+                const unsigned ln = (unsigned)cpgw::opaque(lane);
+#pragma unroll
+                for (int t = 0; t < CPG_GENI_NREGS; t++) cf[t] = cpgw::gld(R.fam_cf, (unsigned)t * 64u + ln);
+                for (unsigned t = (unsigned)lane; t < (unsigned)ldw; t += 64u) w[t] = 0.0;
+#pragma unroll
+                for (int s = 0; s < NSX; s++) { const unsigned i = (unsigned)lane + 64u * (unsigned)s; if (i < n) qs[i] = qv[GENI ? s : 0]; }
+#pragma unroll
+                for (int s = 0; s < NSZ; s++) { const unsigned i = (unsigned)lane + 64u * (unsigned)s; if (i < m) us[i] = uv[GENI ? s : 0]; }
+                cpgw::lds_order();
+            } else factor_in_lds();
+        }
         else
 #endif
         factor_generic();
         if (__builtin_expect(S.debug_stage == 3, 0)) { if (lane == 0) { Bt.status[b] = 11; Bt.iter[b] = 0; } continue; }     // (factorised, coefficients loaded)
+#ifdef CPG_GENI_HEADER
+        if (GENI && __builtin_expect(S.debug_stage == 21, 0)) {
+            // (tests, families with at least 64 primal results: instance b leaves coefficient register b mod NREGS, lane by lane,
+            // in its first 64 primal results -- the family's table against the device's own factorisation)
+            const int rsel = (int)(b % (long long)CPG_GENI_NREGS);
+            double v = 0.0;
+#pragma unroll
+            for (int t = 0; t < CPG_GENI_NREGS; t++) v = t == rsel ? cf[t] : v;
+            if (F0.n_prim >= 64) Bt.prim[(size_t)b * F0.n_prim + (unsigned)lane] = v;
+            if (lane == 0) { Bt.status[b] = 11; Bt.iter[b] = 0; }
+            continue;
+        }
+#endif
         CPG_INST_PROBE();          // 2: factorised, coefficients in registers
 
 #ifdef CPG_GENS_HEADER
@@ -828,12 +900,12 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
 #pragma unroll
         for (int s = 0; s < NSX; s++) {
             const unsigned i = (unsigned)lane + 64u * (unsigned)s;
-            qr[s] = i < n ? cpgw::gld((const double *)B.q, i) : 0.0;
+            qr[s] = GENI ? qv[GENI ? s : 0] : (i < n ? cpgw::gld((const double *)B.q, i) : 0.0);      // (generated instance kernel: no read-back of what this lane just stored)
         }
 #pragma unroll
         for (int s = 0; s < NSZ; s++) {
             const unsigned i = (unsigned)lane + 64u * (unsigned)s;
-            ur[s] = i < m ? cpgw::gld((const double *)B.u, i) : 0.0;
+            ur[s] = GENI ? uv[GENI ? s : 0] : (i < m ? cpgw::gld((const double *)B.u, i) : 0.0);
         }
         const CtxT cx{F, R, B, w, lane, qr, ur, qs, us, shared && F.A_rows.n_chunks > 0};
         double x[NSX], z[NSZ], y[NSZ];
@@ -906,6 +978,8 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
             cpgw::lds_order();
         };
         const int chk_int = S.check_termination, ad_int = S.adaptive_rho ? S.adaptive_rho_interval : 0;
+        bool refactored = false;
+        (void)refactored;
         CPG_INST_PROBE();          // 3: workspace loaded
         // The iterations between two events (termination check, rho adaptation, max_iter) run in their own
         // inner loop: the check (row products, norms, infeasibility tests) needs many registers, and with
@@ -948,7 +1022,12 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
                     }
                     cpgw::mem_order();
 #ifdef CPG_GENI_HEADER
-                    if (GENI) factor_in_lds();
+                    if (GENI) {
+                        factor_in_lds();
+                        // (a whole batch on this kernel: instances that factored in the loop, counted once each)
+                        if (Bt.ho_count && !refactored && lane == 0) (void)cpgw::atomic_next(Bt.ho_count);
+                        refactored = true;
+                    }
                     else
 #endif
                     factor_generic();

@@ -136,7 +136,7 @@ class CpgLibrary:
 
     SYMBOLS = ['cpg_hip_device_count', 'cpg_hip_create_osqp', 'cpg_hip_create_clarabel', 'cpg_hip_destroy', 'cpg_hip_last_error',
                'cpg_hip_status_string', 'cpg_hip_set_default_settings', 'cpg_hip_set_setting',
-               'cpg_hip_get_setting', 'cpg_hip_set_build_option', 'cpg_hip_set_handover', 'cpg_hip_last_phase_ms', 'cpg_hip_set_update', 'cpg_hip_set_refactor', 'cpg_hip_set_refactor_merged', 'cpg_hip_set_shared_registers', 'cpg_hip_set_resident', 'cpg_hip_set_gradient', 'cpg_hip_gradient_batch',
+               'cpg_hip_get_setting', 'cpg_hip_set_build_option', 'cpg_hip_set_handover', 'cpg_hip_last_phase_ms', 'cpg_hip_set_update', 'cpg_hip_set_refactor', 'cpg_hip_set_refactor_merged', 'cpg_hip_set_shared_registers', 'cpg_hip_set_instance_registers', 'cpg_hip_set_resident', 'cpg_hip_set_gradient', 'cpg_hip_gradient_batch',
                'cpg_hip_solve_batch',
                'cpg_hip_solve_batch_device', 'cpg_hip_solve_batch_state', 'cpg_hip_solve_batch_device_state', 'cpg_hip_solve_batches_pipelined', 'cpg_hip_host_malloc',
                'cpg_hip_host_free', 'cpg_hip_synchronize', 'cpg_hip_get_stream', 'cpg_hip_last_kernel_ms',
@@ -169,6 +169,7 @@ class CpgLibrary:
         L.cpg_hip_set_resident.argtypes = [C.c_void_p, C.POINTER(_Refactor), C.POINTER(_Resident)]
         L.cpg_hip_set_refactor_merged.argtypes = [C.c_void_p, C.POINTER(_Refactor), C.POINTER(_Resident)]
         L.cpg_hip_set_shared_registers.argtypes = [C.c_void_p, C.POINTER(_Resident), _dp, C.c_int32, C.c_double, C.c_double]
+        L.cpg_hip_set_instance_registers.argtypes = [C.c_void_p, C.POINTER(_Resident), _dp, C.c_int32, _i8p, C.c_double, C.c_double]
         L.cpg_hip_set_gradient.argtypes = [C.c_void_p, C.POINTER(_Gradient)]
         L.cpg_hip_gradient_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp]
         L.cpg_hip_solve_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]
@@ -819,6 +820,17 @@ class BatchSolver:
                 sol_desc=u32(mg.sol.desc), sol_cols=u16(mg.sol.cols), sol_kind=i32(mg.sol_kind), sol_idx=i32(mg.sol_idx),
                 sol_lcol=i32(mg.sol_lcol), rows_A=none, rows_P=none, rows_At=none, out_ax=0, out_px=0, out_aty=0)
             self.lib.check(self.lib.L.cpg_hip_set_refactor_merged(hh, C.byref(rf), C.byref(ms)), 'cpg_hip_set_refactor_merged')
+            # the family's coefficients of that program (the factor at the family's rho, sigma and row classes, as for the
+            # shared kernel's register executor): the instance kernel starts from them instead of factoring, which lets it
+            # serve a whole batch in one launch (cpg_hip_set_instance_registers)
+            from . import resident_plan as _rs
+            o0 = self.plan.osqp
+            rho, sigma = float(o0.settings['rho']), float(o0.settings['sigma'])
+            ct = np.ascontiguousarray(self._family_ctype, dtype=np.int8)
+            rho_vec = np.where(ct == 1, 1e3 * rho, np.where(ct == 0, rho, 1e-6))
+            coef = np.ascontiguousarray(_rs.replay_solve_vals(mg, _rs.replay_factor(mg, Ps, As, sigma, 1.0 / rho_vec)), dtype=np.float64)
+            self.lib.check(self.lib.L.cpg_hip_set_instance_registers(hh, C.byref(ms), _d(coef), len(coef), ct.ctypes.data_as(_i8p),
+                                                                      rho, sigma), 'cpg_hip_set_instance_registers')
         elif res is not None:
             def rows(prog, ent):
                 return _RowsProgram(n_chunks=prog.n_chunks, nnz=prog.nnz, ctab=i32(prog.ctab), desc=u32(prog.desc), cols=u16(prog.cols), ent=i32(ent))
@@ -870,7 +882,7 @@ class BatchSolver:
     def set_program_placement(self, in_lds: int = -1):
         """-1 automatic, 0 stream the solve program from L2/HBM, 1 keep it resident in LDS, 2 (per-instance factor
         handles) the streaming executor with its entry words in LDS instead of a generated executor, 3 the squad executor,
-        4 the register executor of the shared kernel (include/cpg_hip.h)"""
+        4 the register executor of the shared kernel, 5 the single-kernel step under rho adaptation (include/cpg_hip.h)"""
         self._placement = in_lds
         for hh in (self.h_shared, self.h_ref, self.h_rs):
             if hh is not None and hh.value:

@@ -344,6 +344,23 @@ int cpg_hip_set_refactor_merged(cpg_handle_t h, const cpg_osqp_refactor_t *rf, c
 int cpg_hip_set_shared_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, const double *coef, int32_t n_coef,
                                  double rho, double sigma);
 
+/* Family coefficients of a per-instance factor handle in shared-matrix mode whose generated instance executor runs the
+ * merged program mg (call it behind cpg_hip_set_refactor_merged, which a later cpg_hip_set_refactor* undoes): coef as for
+ * cpg_hip_set_shared_registers, computed for the KKT matrix at rho / sigma with the row classes row_class [m] (1 equality,
+ * 0 inequality, -1 free, canonical order).  The instance kernel then starts an instance from this table instead of
+ * factoring -- only while the instance's workspace rho, the handle's sigma and every row class of the instance are exactly
+ * these; any other instance factors on the device as before.  Any other library: CPG_OK, nothing installed.
+ * This call, like cpg_hip_set_refactor*, waits for h's own stream and for the streams of the shared-factor handles h is
+ * linked to (cpg_hip_set_handover; their solves launch h's kernel on THEIR streams) before it frees the tables it replaces.
+ * With the table installed, a shared-factor handle this handle is linked to (cpg_hip_set_handover) solves a batch under
+ * rho adaptation in ONE launch of the instance kernel over the whole batch instead of the shared-factor kernel plus the
+ * hand-over: placement -1 picks that step where it is usable, 5 forces it, 1 / 3 / 4 keep the two kernels;
+ * cpg_hip_get_setting(shared handle, "single_kernel_step") reports whether a solve would run it.  After such a solve
+ * cpg_hip_last_phase_ms returns its whole time as the first phase, 0 as the second, and the number of instances that
+ * refactored in the loop as the hand-over count. */
+int cpg_hip_set_instance_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, const double *coef, int32_t n_coef,
+                                   const int8_t *row_class, double rho, double sigma);
+
 /* cpg_hip_set_refactor(h, rf), and -- when this library carries the generated resident executor of exactly this
  * family (cvxpygen_amd.codegen.resident_header; the merged program's fingerprint decides) -- the resident kernel's
  * tables: solves then run cpg_osqp_resident.h instead of the streaming kernel.  cpg_hip_get_setting(h,
@@ -416,6 +433,9 @@ int cpg_hip_set_launch(cpg_handle_t h, int waves_per_block, int inst_per_wave, i
  * MI355X, kept selectable for comparison; a solve fails with CPG_E_UNSUPPORTED where the library has none;
  * 4 = shared-factor handles: the register executor (cpg_hip_set_shared_registers), which -1 also picks where it is usable;
  * a solve fails with CPG_E_UNSUPPORTED where it is not.  Per-instance factor handles take 4 as they take 3.
+ * 5 = shared-factor handles under rho adaptation: the single-kernel step (cpg_hip_set_instance_registers), which -1 also
+ * picks where it is usable; such a solve fails with CPG_E_UNSUPPORTED where it is not.  Without rho adaptation, and on
+ * per-instance factor handles, 5 acts as -1.
  * Replaces nothing of the reference's interface: the generated C has one placement, the CPU's (cvxpygen/solvers/osqp.py:62). */
 int cpg_hip_set_program_placement(cpg_handle_t h, int in_lds);
 
