@@ -69,6 +69,12 @@ struct cpg_solver_s {
     bool have_gradient = false;
     std::vector<void *> gradient_owned;
     DevBuf g_theta, g_x, g_y, g_dprim, g_dtheta;
+    // variable table of the device-resident adjoint (cpg_hip_set_gradient_vars): user entry k of an upstream-gradient row
+    // -> canonical x, kept by canonical entry (gv_ptr [n + 1], gv_src: the user entries of each, ascending)
+    const int *gv_ptr = nullptr, *gv_src = nullptr;
+    int n_gv = 0;
+    std::vector<void *> gv_owned;
+    rt_event_t ev_after{};              // cpg_hip_gradient_batch_device: recorded on the stream of the handle to wait for
     cpg::DevSettings S{};
     int waves_per_block = 0, inst_per_wave = 1, blocks_per_cu = 0;
     int program_in_lds = -1;            // -1 auto, 0 stream from L2/HBM, 1 resident in LDS, 3 squad executor (program in registers),
@@ -1123,7 +1129,7 @@ int cpg_hip_create_osqp(const cpg_osqp_family_t *f, int device, cpg_handle_t *ou
         if (h->lds_limit < 160 * 1024 && strstr(prop.gcnArchName, "gfx950")) h->lds_limit = 160 * 1024;
         e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
         if (e != hipSuccess) { set_error(std::string("hipStreamCreate: ") + hipGetErrorString(e)); delete h; return CPG_E_HIP; }
-        hipEventCreate(&h->ev0); hipEventCreate(&h->ev1); hipEventCreate(&h->ev_mid); h->have_events = true;
+        hipEventCreate(&h->ev0); hipEventCreate(&h->ev1); hipEventCreate(&h->ev_mid); hipEventCreate(&h->ev_after); h->have_events = true;
     }
     cpg::DevFamily &F = h->F;
     F.n = f->n; F.m = f->m; F.n_eq = f->n_eq; F.is_max = f->is_maximization;
@@ -1302,7 +1308,7 @@ static int open_device(cpg_handle_t h, int device) {
     if (h->lds_limit < 160 * 1024 && strstr(prop.gcnArchName, "gfx950")) h->lds_limit = 160 * 1024;
     e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { set_error(std::string("hipStreamCreate: ") + hipGetErrorString(e)); return CPG_E_HIP; }
-    hipEventCreate(&h->ev0); hipEventCreate(&h->ev1); hipEventCreate(&h->ev_mid); h->have_events = true;
+    hipEventCreate(&h->ev0); hipEventCreate(&h->ev1); hipEventCreate(&h->ev_mid); hipEventCreate(&h->ev_after); h->have_events = true;
     return CPG_OK;
 }
 
@@ -1604,14 +1610,14 @@ int cpg_hip_destroy(cpg_handle_t h) {
     // (links in both directions end here: neither side keeps a pointer to a destroyed handle)
     if (h->linked) h->linked->linked_from.erase(std::remove(h->linked->linked_from.begin(), h->linked->linked_from.end(), h), h->linked->linked_from.end());
     for (cpg_solver_s *s : h->linked_from) s->linked = nullptr;
-    free_list(h->owned); free_list(h->update_owned); free_list(h->refactor_owned); free_list(h->sreg_owned); free_list(h->ireg_owned); free_list(h->resident_owned); free_list(h->gradient_owned);
+    free_list(h->owned); free_list(h->update_owned); free_list(h->refactor_owned); free_list(h->sreg_owned); free_list(h->ireg_owned); free_list(h->resident_owned); free_list(h->gradient_owned); free_list(h->gv_owned);
     free_buf(h->g_theta); free_buf(h->g_x); free_buf(h->g_y); free_buf(h->g_dprim); free_buf(h->g_dtheta);
     if (h->d_counter) rt_free(h->d_counter);
     free_buf(h->scratch);
     free_buf(h->s_theta); h->s_out.free(); free_buf(h->s_state_in); free_buf(h->s_state_out);
     free_buf(h->ho_state); free_buf(h->ho_list);
     free_pipe(h->pipe); h->pipe = nullptr;
-    if (h->have_events) { hipEventDestroy(h->ev0); hipEventDestroy(h->ev1); hipEventDestroy(h->ev_mid); }
+    if (h->have_events) { hipEventDestroy(h->ev0); hipEventDestroy(h->ev1); hipEventDestroy(h->ev_mid); hipEventDestroy(h->ev_after); }
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
     return CPG_OK;
@@ -2613,23 +2619,36 @@ int cpg_hip_set_gradient(cpg_handle_t h, const cpg_osqp_gradient_t *g) {
     return CPG_OK;
 }
 
-int cpg_hip_gradient_batch(cpg_handle_t h, int64_t B, const double *theta, const double *sol_x, const double *sol_y,
-                           const double *dx, double *dtheta) {
+int cpg_hip_set_gradient_vars(cpg_handle_t h, int32_t n_gv, const int32_t *idx) {
     if (!h || !h->have_gradient) { set_error("cpg_hip_set_gradient has not been called"); return CPG_E_BADARG; }
-    if (B < 0 || !sol_x || !sol_y || !dx || !dtheta || (h->R.np_var > 0 && !theta)) { set_error("null buffer"); return CPG_E_BADARG; }
-    if (B == 0) return CPG_OK;
+    if (n_gv < 0 || (n_gv > 0 && !idx)) { set_error("cpg_hip_set_gradient_vars: n_gv >= 0 and a table of n_gv entries"); return CPG_E_BADARG; }
+    const int n = h->F.n;
+    for (int k = 0; k < n_gv; k++)
+        if (idx[k] < 0 || idx[k] >= n) { set_error("cpg_hip_set_gradient_vars: index outside [0, n)"); return CPG_E_BADARG; }
     int rc = rt_set_device(h->device);
     if (rc) return rc;
-    const size_t b = (size_t)B, n = h->F.n, m = h->F.m, N = n + m;
-    if ((rc = ensure(h->g_theta, b * h->R.np_var * sizeof(double)))) return rc;
-    if ((rc = ensure(h->g_x, b * n * sizeof(double)))) return rc;
-    if ((rc = ensure(h->g_y, b * m * sizeof(double)))) return rc;
-    if ((rc = ensure(h->g_dprim, b * n * sizeof(double)))) return rc;
-    if ((rc = ensure(h->g_dtheta, b * h->Gd.NP * sizeof(double)))) return rc;
-    if ((rc = rt_h2d(h, h->g_theta.p, theta, b * h->R.np_var * sizeof(double)))) return rc;
-    if ((rc = rt_h2d(h, h->g_x.p, sol_x, b * n * sizeof(double)))) return rc;
-    if ((rc = rt_h2d(h, h->g_y.p, sol_y, b * m * sizeof(double)))) return rc;
-    if ((rc = rt_h2d(h, h->g_dprim.p, dx, b * n * sizeof(double)))) return rc;
+    if ((rc = rt_sync(h))) return rc;                             // (an adjoint in flight may still read the old table)
+    free_list(h->gv_owned);
+    h->gv_ptr = h->gv_src = nullptr; h->n_gv = 0;
+    if (n_gv == 0) return CPG_OK;
+    // by canonical entry, the user entries of each in ascending order (a counting sort keeps them so)
+    std::vector<int> ptr((size_t)n + 1, 0), src((size_t)n_gv);
+    for (int k = 0; k < n_gv; k++) ptr[(size_t)idx[k] + 1]++;
+    for (int i = 0; i < n; i++) ptr[(size_t)i + 1] += ptr[(size_t)i];
+    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    for (int k = 0; k < n_gv; k++) src[(size_t)fill[(size_t)idx[k]]++] = k;
+    if ((rc = upload<int>(h, h->gv_owned, ptr.data(), ptr.size(), &h->gv_ptr))) return rc;
+    if ((rc = upload<int>(h, h->gv_owned, src.data(), src.size(), &h->gv_src))) return rc;
+    if ((rc = rt_sync(h))) return rc;                             // (the uploads read host vectors that end here)
+    h->n_gv = n_gv;
+    return CPG_OK;
+}
+
+// The adjoint kernel over device buffers, queued on h's stream between ev0 and ev1.  d_up: the upstream gradient -- canonical
+// [B][n], or [B][n_gv] in the caller's variable layout when use_table (the kernel then scatters through h's table).
+static int launch_gradient_batch(cpg_handle_t h, int64_t B, const double *d_theta, const double *d_x, const double *d_y,
+                                 const double *d_up, bool use_table, double *d_dtheta) {
+    const size_t n = h->F.n, m = h->F.m, N = n + m;
     // workgroup shape: the LDS vectors of a wavefront bound the residency; W waves per workgroup and
     // per_cu workgroups are chosen to keep as many wavefronts resident as LDS and the register budget
     // (4 x CPG_GRADIENT_WAVES_PER_SIMD per CU) allow -- the kernel waits on dependent loads
@@ -2643,18 +2662,60 @@ int cpg_hip_gradient_batch(cpg_handle_t h, int64_t B, const double *theta, const
     }
     const size_t lds = (size_t)W * per_wave * sizeof(double);
     const int blocks = grid_blocks(h, B, W, per_cu);
+    int rc;
+    // (growing the scratch frees the old block while earlier work queued on this stream may still use it: safe because hipFree
+    // waits for the device -- the one point at which the asynchronous entry point can involve the host, first call or larger B)
     if ((rc = ensure(h->scratch, (size_t)blocks * W * (size_t)h->R.buf_doubles * sizeof(double)))) return rc;
     cpg::DevGradBatch Bt;
-    Bt.B = B; Bt.theta = (const double *)h->g_theta.p; Bt.sol_x = (const double *)h->g_x.p;
-    Bt.sol_y = (const double *)h->g_y.p; Bt.dx = (const double *)h->g_dprim.p; Bt.dtheta = (double *)h->g_dtheta.p;
+    Bt.B = B; Bt.theta = d_theta; Bt.sol_x = d_x; Bt.sol_y = d_y; Bt.dtheta = d_dtheta;
+    Bt.dx = use_table ? nullptr : d_up;
+    if (use_table) { Bt.dvars = d_up; Bt.gv_ptr = h->gv_ptr; Bt.gv_idx = h->gv_src; Bt.n_gv = h->n_gv; }
     Bt.counter = h->d_counter; Bt.scratch = (double *)h->scratch.p;
     RT_CHECK(hipMemsetAsync(h->d_counter, 0, sizeof(unsigned), h->stream));
     RT_CHECK(hipEventRecord(h->ev0, h->stream));
     rc = launch_gradient(h, Bt, blocks, W, lds);
     if (rc) return rc;
     RT_CHECK(hipEventRecord(h->ev1, h->stream));
+    return CPG_OK;
+}
+
+int cpg_hip_gradient_batch(cpg_handle_t h, int64_t B, const double *theta, const double *sol_x, const double *sol_y,
+                           const double *dx, double *dtheta) {
+    if (!h || !h->have_gradient) { set_error("cpg_hip_set_gradient has not been called"); return CPG_E_BADARG; }
+    if (B < 0 || !sol_x || !sol_y || !dx || !dtheta || (h->R.np_var > 0 && !theta)) { set_error("null buffer"); return CPG_E_BADARG; }
+    if (B == 0) return CPG_OK;
+    int rc = rt_set_device(h->device);
+    if (rc) return rc;
+    const size_t b = (size_t)B, n = h->F.n, m = h->F.m;
+    if ((rc = ensure(h->g_theta, b * h->R.np_var * sizeof(double)))) return rc;
+    if ((rc = ensure(h->g_x, b * n * sizeof(double)))) return rc;
+    if ((rc = ensure(h->g_y, b * m * sizeof(double)))) return rc;
+    if ((rc = ensure(h->g_dprim, b * n * sizeof(double)))) return rc;
+    if ((rc = ensure(h->g_dtheta, b * h->Gd.NP * sizeof(double)))) return rc;
+    if ((rc = rt_h2d(h, h->g_theta.p, theta, b * h->R.np_var * sizeof(double)))) return rc;
+    if ((rc = rt_h2d(h, h->g_x.p, sol_x, b * n * sizeof(double)))) return rc;
+    if ((rc = rt_h2d(h, h->g_y.p, sol_y, b * m * sizeof(double)))) return rc;
+    if ((rc = rt_h2d(h, h->g_dprim.p, dx, b * n * sizeof(double)))) return rc;
+    if ((rc = launch_gradient_batch(h, B, (const double *)h->g_theta.p, (const double *)h->g_x.p, (const double *)h->g_y.p,
+                                    (const double *)h->g_dprim.p, false, (double *)h->g_dtheta.p))) return rc;
     if ((rc = rt_d2h(h, dtheta, h->g_dtheta.p, b * h->Gd.NP * sizeof(double)))) return rc;
     return rt_sync(h);
+}
+
+int cpg_hip_gradient_batch_device(cpg_handle_t h, int64_t B, const double *d_theta, const double *d_sol_x, const double *d_sol_y,
+                                  const double *d_dvars, double *d_dtheta, cpg_handle_t after) {
+    if (!h || !h->have_gradient) { set_error("cpg_hip_set_gradient has not been called"); return CPG_E_BADARG; }
+    if (B < 0 || !d_sol_x || !d_sol_y || !d_dvars || !d_dtheta || (h->R.np_var > 0 && !d_theta)) { set_error("null buffer"); return CPG_E_BADARG; }
+    if (after && after->device != h->device) { set_error("cpg_hip_gradient_batch_device: `after` is a handle of another device"); return CPG_E_BADARG; }
+    if (B == 0) return CPG_OK;
+    int rc = rt_set_device(h->device);
+    if (rc) return rc;
+    if (after && after != h) {
+        // everything queued on after's stream so far -- the forward solve that writes d_sol_x / d_sol_y -- comes first
+        RT_CHECK(hipEventRecord(h->ev_after, after->stream));
+        RT_CHECK(hipStreamWaitEvent(h->stream, h->ev_after, 0));
+    }
+    return launch_gradient_batch(h, B, d_theta, d_sol_x, d_sol_y, d_dvars, h->n_gv > 0, d_dtheta);
 }
 
 int cpg_hip_set_launch(cpg_handle_t h, int waves_per_block, int inst_per_wave, int blocks_per_cu) {

@@ -1072,6 +1072,12 @@ struct DevGradient {
 struct DevGradBatch {
     long long B;
     const double *theta, *sol_x, *sol_y, *dx;    // dx: upstream gradient scattered to canonical x [B][n]
+    // device-resident entry point with a variable table (cpg_hip_set_gradient_vars): the upstream gradient in the caller's
+    // layout, dvars [B][n_gv], and the table by canonical entry -- entry i of x sums dvars[b][gv_idx[t]] over
+    // t = gv_ptr[i] .. gv_ptr[i + 1] - 1, gv_idx ascending within an entry.  gv_ptr == nullptr: dx is read as it is.
+    const double *dvars = nullptr;
+    const int *gv_ptr = nullptr, *gv_idx = nullptr;
+    int n_gv = 0;
     double *dtheta;
     unsigned *counter;
     double *scratch;
@@ -1106,7 +1112,23 @@ CPG_DEV void osqp_gradient_body(const DevFamily &F, const DevRefactor &R, const 
         const size_t b = (size_t)ig;
         const double *theta = Bt.theta + b * (size_t)R.np_var;
         // ---- solution, active set, upstream gradient (cpg_update_d<var>: scatter to canonical x)
-        for (unsigned i = (unsigned)lane; i < n; i += 64u) { xs[i] = cpgw::gld(Bt.sol_x + b * n, i); dxs[i] = cpgw::gld(Bt.dx + b * n, i); }
+        if (Bt.gv_ptr) {
+            // every lane owns its canonical entries and sums their user entries in ascending order: no two lanes meet in
+            // dxs, the order of the sum is fixed, an entry with one source takes its bits, one with none is +0.0
+            const double *dv = Bt.dvars + b * (size_t)Bt.n_gv;
+            for (unsigned i = (unsigned)lane; i < n; i += 64u) {
+                xs[i] = cpgw::gld(Bt.sol_x + b * n, i);
+                const unsigned a0 = (unsigned)cpgw::gld(Bt.gv_ptr, i), e0 = (unsigned)cpgw::gld(Bt.gv_ptr, i + 1u);
+                double acc = 0.0;
+                if (a0 < e0) {
+                    acc = cpgw::gld(dv, (unsigned)cpgw::gld(Bt.gv_idx, a0));
+                    for (unsigned t = a0 + 1u; t < e0; t++) acc += cpgw::gld(dv, (unsigned)cpgw::gld(Bt.gv_idx, t));
+                }
+                dxs[i] = acc;
+            }
+        } else {
+            for (unsigned i = (unsigned)lane; i < n; i += 64u) { xs[i] = cpgw::gld(Bt.sol_x + b * n, i); dxs[i] = cpgw::gld(Bt.dx + b * n, i); }
+        }
         for (unsigned i = (unsigned)lane; i < m; i += 64u) {
             const double yi = cpgw::gld(Bt.sol_y + b * m, i);
             ys[i] = yi;

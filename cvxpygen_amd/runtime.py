@@ -137,6 +137,7 @@ class CpgLibrary:
     SYMBOLS = ['cpg_hip_device_count', 'cpg_hip_create_osqp', 'cpg_hip_create_clarabel', 'cpg_hip_destroy', 'cpg_hip_last_error',
                'cpg_hip_status_string', 'cpg_hip_set_default_settings', 'cpg_hip_set_setting',
                'cpg_hip_get_setting', 'cpg_hip_set_build_option', 'cpg_hip_set_handover', 'cpg_hip_last_phase_ms', 'cpg_hip_set_update', 'cpg_hip_set_refactor', 'cpg_hip_set_refactor_merged', 'cpg_hip_set_shared_registers', 'cpg_hip_set_instance_registers', 'cpg_hip_set_resident', 'cpg_hip_set_gradient', 'cpg_hip_gradient_batch',
+               'cpg_hip_set_gradient_vars', 'cpg_hip_gradient_batch_device',
                'cpg_hip_solve_batch',
                'cpg_hip_solve_batch_device', 'cpg_hip_solve_batch_state', 'cpg_hip_solve_batch_device_state', 'cpg_hip_solve_batches_pipelined', 'cpg_hip_host_malloc',
                'cpg_hip_host_free', 'cpg_hip_synchronize', 'cpg_hip_get_stream', 'cpg_hip_last_kernel_ms',
@@ -172,6 +173,8 @@ class CpgLibrary:
         L.cpg_hip_set_instance_registers.argtypes = [C.c_void_p, C.POINTER(_Resident), _dp, C.c_int32, _i8p, C.c_double, C.c_double]
         L.cpg_hip_set_gradient.argtypes = [C.c_void_p, C.POINTER(_Gradient)]
         L.cpg_hip_gradient_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp]
+        L.cpg_hip_set_gradient_vars.argtypes = [C.c_void_p, C.c_int32, _ip]
+        L.cpg_hip_gradient_batch_device.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
         L.cpg_hip_solve_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]
         L.cpg_hip_solve_batch_device.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
         L.cpg_hip_solve_batch_state.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]
@@ -538,6 +541,7 @@ class BatchSolver:
         self._rplan_g = None               # canonicalisation and the gradients, pruned pattern for the factor (see _ensure_refactor_handle)
         self._rg_key = None
         self._grad_loaded_on = set()
+        self._gv_installed = {}            # gradient handle -> variable table installed on it (cpg_hip_set_gradient_vars)
         self._hybrid = False
         self._shared_cand = None           # refactor_plan.shared_mode_plan of this family (h_rs and the register executor)
         self._sreg_done = False
@@ -1003,6 +1007,28 @@ class BatchSolver:
         self.lib.check(self.lib.L.cpg_hip_set_gradient(hh, C.byref(g)), 'cpg_hip_set_gradient')
         self._gradient_keep = getattr(self, '_gradient_keep', []) + [keep]
 
+    def _gradient_handle(self, names, cols, th_fixed, at_theta0: bool, q_setup: Optional[np.ndarray] = None):
+        """the handle an adjoint over these varying parameters runs on, its factor tables and adjoint tables loaded"""
+        dep = self.desc.user_p_name_to_canon_outdated()
+        touched = set().union(*[dep[nm] for nm in names]) if names else set()
+        # matrices at their code-generation-time values in every instance: the masked KKT matrix is factored on the
+        # numerically non-zero pattern (handle h_rg); otherwise on the stored one (h_ref, shared with the solve path)
+        pruned = at_theta0 and not (touched & {'P', 'A'}) and os.environ.get('CPG_PRUNE', '1') != '0'
+        if pruned:
+            self._set_refactor(cols, th_fixed, None, mode='grad')
+            hg = self.h_rg
+        else:
+            before = self._ref_key
+            self._set_refactor(cols, th_fixed, q_setup)     # no-op when these tables are loaded
+            if self._ref_key != before:
+                self._update_key = None          # a following solve must re-select its tables
+            hg = self.h_ref
+        if hg.value not in self._grad_loaded_on:
+            self._set_gradient(hg)
+            self._grad_loaded_on.add(hg.value)
+        self.h_grad = hg
+        return hg
+
     def gradient(self, params: Dict[str, np.ndarray], sol_x: np.ndarray, sol_y: np.ndarray,
                  dvars: Dict[str, np.ndarray], updated_params: Optional[Sequence[str]] = None,
                  theta_base: Optional[np.ndarray] = None) -> Dict[str, np.ndarray]:
@@ -1018,24 +1044,7 @@ class BatchSolver:
         fixed = np.ones(desc.NP + 1, dtype=bool)
         fixed[cols] = False
         base = desc.theta0 if theta_base is None else np.asarray(theta_base, dtype=np.float64)
-        dep = desc.user_p_name_to_canon_outdated()
-        touched = set().union(*[dep[nm] for nm in names]) if names else set()
-        # matrices at their code-generation-time values in every instance: the masked KKT matrix is factored on the
-        # numerically non-zero pattern (handle h_rg); otherwise on the stored one (h_ref, shared with the solve path)
-        pruned = theta_base is None and not (touched & {'P', 'A'}) and os.environ.get('CPG_PRUNE', '1') != '0'
-        if pruned:
-            self._set_refactor(cols, np.where(fixed, base, 0.0), None, mode='grad')
-            hg = self.h_rg
-        else:
-            before = self._ref_key
-            self._set_refactor(cols, np.where(fixed, base, 0.0), None)     # no-op when these tables are loaded
-            if self._ref_key != before:
-                self._update_key = None          # a following solve must re-select its tables
-            hg = self.h_ref
-        if hg.value not in self._grad_loaded_on:
-            self._set_gradient(hg)
-            self._grad_loaded_on.add(hg.value)
-        self.h_grad = hg
+        hg = self._gradient_handle(names, cols, np.where(fixed, base, 0.0), theta_base is None)
         tv = self.theta_var(params, names=names)      # (the solve-side selection -- _updated_names, _var_cols -- stays as it is)
         B = sol_x.shape[0]
         dx = np.zeros((B, desc.n_var))
@@ -1049,8 +1058,13 @@ class BatchSolver:
         tv = np.ascontiguousarray(tv, dtype=np.float64)
         self.lib.check(self.lib.L.cpg_hip_gradient_batch(hg, B, _d(tv), _d(sx), _d(sy), _d(dx), _d(dth)),
                        'cpg_hip_gradient_batch')
+        return self._gradient_dict(dth)
+
+    def _gradient_dict(self, dth: np.ndarray) -> Dict[str, np.ndarray]:
+        """dtheta [B, NP] and its per-parameter views, reshaped like the reference's `param.gradient`"""
+        B = dth.shape[0]
         out = {'_flat': dth}
-        for q in desc.params:
+        for q in self.desc.params:
             blk = dth[:, q.col:q.col + q.size]
             if q.kind == 'dense' and len(q.shape) > 1:
                 blk = blk.reshape((B,) + tuple(q.shape)[::-1]).transpose((0,) + tuple(range(len(q.shape), 0, -1)))
@@ -1339,6 +1353,142 @@ def _last_phase_ms(self):
     return float(a.value), float(b.value), int(n.value)
 
 
+class DeviceGradBatch:
+    """Device-resident buffers of `BatchSolver.gradient_device`: the upstream gradient `dvars` in and `dtheta` out, both in
+    HBM.  theta_var, sol_x and sol_y are borrowed from the `DeviceBatch` of the forward solve (a full_output solver leaves
+    the canonical solution in its prim / dual buffers).  Bound, like that one, to the parameter set selected when it was
+    created.
+
+    dvars [B][n_gv]: the user variables concatenated in the order and flattening of `BatchResult.prim_flat` (F-order per
+    variable); with canonical=True it is [B][n] on the canonical variables and the kernel scatters nothing.
+    dtheta [B][NP]: the layout of `gradient()['_flat']`."""
+
+    def __init__(self, solver: BatchSolver, B: int, canonical: bool = False):
+        if solver._update_key is None:
+            raise ValueError('select the updated parameters first (set_updated, or a solve)')
+        d = solver.desc
+        self.s, self.B, self.canonical = solver, int(B), bool(canonical)
+        self._key = solver._update_key
+        self.gv_idx = np.zeros(0, dtype=np.int32) if canonical or not d.variables else \
+            np.ascontiguousarray(np.concatenate([v.indices for v in d.variables]), dtype=np.int32)
+        self.n_dvars = d.n_var if canonical else int(self.gv_idx.size)
+        self.NP = d.NP
+        self._hg = None                 # the handle the most recent adjoint was queued on
+        self._ptrs = {}
+        for k, nbytes in dict(dvars=self.B * max(self.n_dvars, 1) * 8, dtheta=self.B * max(self.NP, 1) * 8).items():
+            p = C.c_void_p()
+            solver.lib.check(solver.lib.L.cpg_hip_malloc(solver.h_shared, nbytes, C.byref(p)), 'cpg_hip_malloc')
+            self._ptrs[k] = p
+
+    @property
+    def dvars_ptr(self) -> int:
+        """device address of dvars [B][n_dvars] (float64, C order) -- what a GPU tensor's data_ptr() would be"""
+        return int(self._ptrs['dvars'].value)
+
+    @property
+    def dtheta_ptr(self) -> int:
+        """device address of dtheta [B][NP] (float64, C order)"""
+        return int(self._ptrs['dtheta'].value)
+
+    @property
+    def stream(self) -> int:
+        """the HIP stream the adjoint was queued on (hipStream_t as an integer)"""
+        st = C.c_void_p()
+        self.s.lib.check(self.s.lib.L.cpg_hip_get_stream(self._handle(), C.byref(st)), 'cpg_hip_get_stream')
+        return int(st.value or 0)
+
+    def _handle(self):
+        if self._hg is None:
+            raise RuntimeError('no adjoint has been queued on this DeviceGradBatch (BatchSolver.gradient_device)')
+        return self._hg
+
+    def upload_dvars(self, dvars) -> None:
+        """dvars: [B, n_dvars] array, or (not canonical) a dict of per-variable arrays as `gradient()` takes them -- a
+        variable that is missing has gradient zero.  Synchronous."""
+        s, B = self.s, self.B
+        if isinstance(dvars, dict):
+            if self.canonical:
+                raise ValueError('a canonical DeviceGradBatch takes the [B, n] array')
+            blocks = []
+            for v in s.desc.variables:
+                if v.name in dvars:
+                    g = np.asarray(dvars[v.name], dtype=np.float64).reshape((B,) + tuple(v.shape))
+                    blocks.append(g.transpose((0,) + tuple(range(len(v.shape), 0, -1))).reshape(B, -1)
+                                  if len(v.shape) > 1 else g.reshape(B, -1))
+                else:
+                    blocks.append(np.zeros((B, v.indices.size)))
+            dvars = np.concatenate(blocks, axis=1) if blocks else np.zeros((B, 0))
+        a = np.ascontiguousarray(dvars, dtype=np.float64)
+        if a.shape != (B, self.n_dvars):
+            raise ValueError(f'dvars must have shape ({B}, {self.n_dvars}), got {a.shape}')
+        if a.size:
+            s.lib.check(s.lib.L.cpg_hip_memcpy_h2d(s.h_shared, self._ptrs['dvars'], a.ctypes.data_as(C.c_void_p), a.nbytes), 'h2d')
+
+    def synchronize(self) -> None:
+        """waits for the adjoint (the gradient handle's stream; the forward solve it was ordered behind is then done too)"""
+        self.s.lib.check(self.s.lib.L.cpg_hip_synchronize(self._handle()), 'cpg_hip_synchronize')
+
+    def last_kernel_ms(self) -> float:
+        ms = C.c_float(0)
+        self.s.lib.check(self.s.lib.L.cpg_hip_last_kernel_ms(self._handle(), C.byref(ms)), 'cpg_hip_last_kernel_ms')
+        return float(ms.value)
+
+    def download(self) -> Dict[str, np.ndarray]:
+        """the dict `gradient()` returns: '_flat' [B, NP] and every parameter's reshaped view.  Waits for the adjoint."""
+        s = self.s
+        dth = np.empty((self.B, self.NP))
+        hg = self._handle()
+        if dth.nbytes:      # (queued on the gradient handle's stream, behind the kernel)
+            s.lib.check(s.lib.L.cpg_hip_memcpy_d2h(hg, dth.ctypes.data_as(C.c_void_p), self._ptrs['dtheta'], dth.nbytes), 'd2h')
+        else:
+            self.synchronize()
+        return s._gradient_dict(dth)
+
+    def free(self) -> None:
+        for p in self._ptrs.values():
+            self.s.lib.L.cpg_hip_free(self.s.h_shared, p)
+        self._ptrs = {}
+
+
+def _gradient_device(self, dev: DeviceBatch, gdev: DeviceGradBatch, dvars_ptr: Optional[int] = None,
+                     dtheta_ptr: Optional[int] = None) -> None:
+    """Batched `cpg_gradient` on device buffers: the adjoint of the solve that `solve_device(dev)` queued, read from dev's
+    theta / prim / dual buffers, upstream gradient from gdev's dvars, result into gdev's dtheta.  Asynchronous, and ordered
+    behind everything queued on the solving handle's stream so far WITHOUT a host synchronisation; wait with
+    `gdev.synchronize()` / `gdev.download()` -- also before the next `solve_device(dev)`, which overwrites what the adjoint
+    reads.  dvars_ptr / dtheta_ptr: device addresses of the caller's own buffers (same layouts) instead of gdev's.
+    Instances a shared-factor solve flagged for the host (row-class changes, `DeviceBatch.download`) have no solution on
+    the device and therefore no gradient."""
+    if not self.full_output:
+        raise ValueError('the device-resident adjoint needs the canonical solution: BatchSolver(full_output=True)')
+    if dev.s is not self or gdev.s is not self:
+        raise ValueError('DeviceBatch / DeviceGradBatch of another solver')
+    dev.check_current()
+    if gdev._key != self._update_key:
+        raise ValueError('the solver\'s set of updated parameters changed after this DeviceGradBatch was created')
+    if gdev.B != dev.B:
+        raise ValueError(f'batch sizes differ: DeviceBatch {dev.B}, DeviceGradBatch {gdev.B}')
+    key = self._update_key
+    # the handle gradient() would pick for this parameter set.  One difference: where the adjoint shares h_ref with the solve
+    # (matrix parameters), gradient() loads the tables with the default q_setup; here they keep the solve's q_setup -- the
+    # adjoint kernel does not read it, and the key stays the one of the solve, so nothing is reloaded under a solve in flight
+    hg = self._gradient_handle(self._updated_names, self._var_cols, self._th_fixed, key[3] is None, self._q_setup)
+    if self.h.value != self.h_ref.value:
+        self._update_key = key          # (tables went to another handle than the solving one: its selection stands)
+    L = self.lib.L
+    installed, tab = self._gv_installed, gdev.gv_idx
+    if installed.get(hg.value) != tab.tobytes():
+        self.lib.check(L.cpg_hip_set_gradient_vars(hg, int(tab.size), tab.ctypes.data_as(_ip) if tab.size else None),
+                       'cpg_hip_set_gradient_vars')
+        installed[hg.value] = tab.tobytes()
+    P = dev._ptrs
+    gdev._hg = hg
+    self.lib.check(L.cpg_hip_gradient_batch_device(
+        hg, dev.B, P['theta'], P['prim'], P['dual'], C.c_void_p(dvars_ptr) if dvars_ptr else gdev._ptrs['dvars'],
+        C.c_void_p(dtheta_ptr) if dtheta_ptr else gdev._ptrs['dtheta'], self.h), 'cpg_hip_gradient_batch_device')
+
+
+BatchSolver.gradient_device = _gradient_device
 BatchSolver.last_phase_ms = _last_phase_ms
 BatchSolver.solve_device = _solve_device
 BatchSolver.synchronize = _synchronize

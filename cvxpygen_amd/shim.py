@@ -306,3 +306,53 @@ class GeneratedSolver:
 
     def cpg_gradient_batch(self, params, sol_x, sol_y, dvars, updated_params=None):
         return self.batch_solver.gradient(params, sol_x, sol_y, dvars, updated_params)
+
+    def cpg_solve_and_gradient_device(self, params, dvars_fn, updated_params=None, **kwargs):
+        """One training step on device buffers: the batched forward solve and, queued behind it without a host
+        synchronisation, its adjoint (runtime.DeviceBatch / DeviceGradBatch, kept between calls of the same batch size
+        and parameter set).  dvars_fn(dev, gdev) supplies the upstream gradient between the two launches: it either
+        writes [B][n_dvars] doubles to `gdev.dvars_ptr` itself, on a stream ordered before `BatchSolver.gradient_device`
+        is called (a loss that lives on the GPU; the solution is at dev's prim / dual buffers, in order behind the
+        solving handle's stream) and returns None, or returns the array / per-variable dict for `gdev.upload_dvars`
+        (`dev.download()` gives it the solution).  Returns (dev, gdev): `gdev.download()` is the dict
+        `cpg_gradient_batch` returns, `dev.download()` the BatchResult.  The next call waits for this step's adjoint before
+        it overwrites the buffers; `free_device_step()` releases them."""
+        if not self.gradient:
+            raise AttributeError('code was generated with gradient=False')
+        bs = self.batch_solver
+        if type(bs) is not BatchSolver or not bs.full_output:
+            raise ValueError('the device-resident step needs an OSQP solver generated with gradient=True (two-stage and '
+                             'conic solvers solve on another kernel: use cpg_solve_batch / cpg_gradient_batch)')
+        if updated_params is None:
+            updated_params = [p for p in self.desc.param_names if p in params] or None
+        cached = getattr(self, '_dev_step', None)
+        if cached is not None and cached[3] is not bs:
+            cached = self._dev_step = None          # (buffers of a solver that is gone: freed with its device context)
+        if cached is not None and cached[2]._hg is not None:
+            cached[2].synchronize()                 # the previous step's adjoint still reads what this solve overwrites
+        bs.set_updated(updated_params)
+        bs.apply_settings(**self._filter_settings(kwargs))
+        tv = bs.theta_var(params)
+        B = tv.shape[0]
+        from .runtime import DeviceBatch, DeviceGradBatch
+        if cached is None or cached[0] != (B, bs._update_key):
+            if cached is not None:
+                cached[1].free(); cached[2].free()
+            cached = self._dev_step = ((B, bs._update_key), DeviceBatch(bs, B), DeviceGradBatch(bs, B), bs)
+        _, dev, gdev, _ = cached
+        dev.upload(tv)
+        bs.solve_device(dev)
+        up = dvars_fn(dev, gdev)
+        if up is not None:
+            gdev.upload_dvars(up)
+        bs.gradient_device(dev, gdev)
+        return dev, gdev
+
+    def free_device_step(self) -> None:
+        """releases the device buffers `cpg_solve_and_gradient_device` keeps between calls"""
+        cached = getattr(self, '_dev_step', None)
+        self._dev_step = None
+        if cached is not None and cached[3] is self._bs and self._bs.h_shared.value:
+            if cached[2]._hg is not None:
+                cached[2].synchronize()
+            cached[1].free(); cached[2].free()

@@ -381,6 +381,23 @@ int cpg_hip_set_gradient(cpg_handle_t h, const cpg_osqp_gradient_t *g);
  * gradient w.r.t. every user parameter.  Host buffers. */
 int cpg_hip_gradient_batch(cpg_handle_t h, int64_t B, const double *theta_var, const double *sol_x,
                            const double *sol_y, const double *dx, double *dtheta);
+/* Variable table of the device-resident adjoint: idx [n_gv], the canonical x index of entry k of the caller's
+ * upstream-gradient row -- the user variables concatenated in the order and flattening of the forward's prim output
+ * (BatchResult.prim_flat).  The kernel then does the cpg_update_d<var> scatter itself.  Sticky until replaced;
+ * n_gv == 0: the upstream gradient is already canonical [B][n].  Indices outside [0, n) are refused (CPG_E_BADARG);
+ * an index may repeat (a symmetric variable maps two user entries to one canonical entry): its user entries are summed
+ * in ascending k, so the result does not depend on the launch.  Requires cpg_hip_set_gradient on the same handle. */
+int cpg_hip_set_gradient_vars(cpg_handle_t h, int32_t n_gv, const int32_t *idx);
+/* Device-resident cpg_hip_gradient_batch: every pointer is device memory on the handle's device.  d_theta_var
+ * [B][np_var], d_sol_x [B][n], d_sol_y [B][m] (a full-output forward solve leaves them in its d_prim / d_dual),
+ * d_dvars [B][n_gv] in the layout of cpg_hip_set_gradient_vars ([B][n] canonical without a table), d_dtheta [B][NP].
+ * Asynchronous on h's stream; pair with cpg_hip_synchronize(h).  `after` (NULL allowed): a handle of the same device
+ * whose stream h's stream waits for -- an event recorded on it at the time of this call --, so that an adjoint queued
+ * behind a forward solve on another handle needs no host synchronisation in between; after == h and NULL order
+ * nothing.  The reverse order is the caller's: synchronise h before the forward handle overwrites the buffers this
+ * call reads.  cpg_hip_last_kernel_ms(h) reports the adjoint kernel. */
+int cpg_hip_gradient_batch_device(cpg_handle_t h, int64_t B, const double *d_theta_var, const double *d_sol_x,
+                                  const double *d_sol_y, const double *d_dvars, double *d_dtheta, cpg_handle_t after);
 
 /* ---- solve ---------------------------------------------------------------------------------- */
 /* Host buffers: theta_var [B][np_var]; outputs prim [B][n_prim], dual [B][n_dual], obj/pri_res/
