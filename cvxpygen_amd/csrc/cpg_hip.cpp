@@ -1397,9 +1397,11 @@ static bool conic_dims_equal(const cpg::DevConic &a, const cpg::DevConic &b) {
 // [step / 4][lane][4] (lanes without an entry read the zero slot) and output slots [chunk / 4][lane][4] (lanes
 // without a row store to dummy slots chosen per 16-lane store group so that they add no bank conflict; segmented
 // chunks carry their segment mask above bit 13).  `steps`: {first entry, active lanes} in execution order.
+// row_bytes (a header with <prefix>_LEAN, codegen.emit_instance_program): the output-slot table holds byte offsets, 8 x slot,
+// and no segment mask -- ready to be added to the work vector's address like an operand offset.
 static bool generated_tables(const int *ctab, const unsigned *desc, const unsigned short *cols, int n_chunks, int nnz, int n_slots,
                              const int (*steps)[4], int T, std::vector<unsigned short> &gcols, std::vector<unsigned short> &grows,
-                             const int *chunk_shift = nullptr) {
+                             const int *chunk_shift = nullptr, bool row_bytes = false) {
     // steps carry {first entry, active lanes, coefficient register, lane shift of the chunk}: narrow chunks sit at a
     // lane offset so that several steps share one coefficient register (codegen.pack_step_registers); `chunk_shift` is the
     // same shift per chunk, for the output-slot table
@@ -1433,12 +1435,18 @@ static bool generated_tables(const int *ctab, const unsigned *desc, const unsign
                     const int j = nxt < CPG_GEN_DUMMY_SLOTS ? nxt++ : (t & (CPG_GEN_DUMMY_SLOTS - 1));
                     slot = (unsigned)(n_slots + j);
                 }
-                grows[((size_t)(c >> 2) * 64 + t) * 4 + (c & 3)] = (unsigned short)(slot | ((seg ? (d >> 28) : 0u) << 13));       // (every lane of a row carries its segment mask)
+                grows[((size_t)(c >> 2) * 64 + t) * 4 + (c & 3)] = row_bytes ? (unsigned short)(slot * 8u)       // (<= zero_off: checked above)
+                    : (unsigned short)(slot | ((seg ? (d >> 28) : 0u) << 13));       // (every lane of a row carries its segment mask)
             }
         }
     }
     return true;
 }
+#ifdef CPG_GENI_LEAN
+static const bool geni_row_bytes = true;
+#else
+static const bool geni_row_bytes = false;
+#endif
 static unsigned program_fingerprint(const int *ctab, const unsigned *desc, const unsigned short *cols, int n_chunks, int nnz) {
     unsigned hsh = 0x811C9DC5u;
     auto mix = [&](const void *p, size_t nbytes) { const unsigned char *b = (const unsigned char *)p;
@@ -1720,7 +1728,7 @@ static int set_instance_executor(cpg_handle_t h, const cpg_osqp_refactor_t *r, c
                 if (h->rows_hdr[k][4 * c2] != cpg::GeniRows::len(k, c2) || h->rows_hdr[k][4 * c2 + 3] != cpg::GeniRows::off(k, c2)) ok = false;
         }
     }
-    if (ok) ok = generated_tables(g.sol_ctab, g.sol_desc, g.sol_cols, g.sol_chunks, g.sol_nnz, g.sol_slots, steps, CPG_GENI_NSTEPS, gcols, grows, chunk_shift);
+    if (ok) ok = generated_tables(g.sol_ctab, g.sol_desc, g.sol_cols, g.sol_chunks, g.sol_nnz, g.sol_slots, steps, CPG_GENI_NSTEPS, gcols, grows, chunk_shift, geni_row_bytes);
     if (ok) {
         // coefficient sources per (register, lane): the steps that share a register occupy disjoint lane ranges
         gsrc.assign((size_t)CPG_GENI_NREGS * 64, 0u);
@@ -2044,7 +2052,7 @@ int cpg_hip_set_shared_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, 
     static const int chunk_shift[] = CPG_GENI_CHUNK_SHIFT;
     std::vector<unsigned short> gcols, grows;
     if (!generated_tables(mg->sol_ctab, mg->sol_desc, mg->sol_cols, mg->sol_chunks, mg->sol_nnz, mg->sol_slots, steps, CPG_GENI_NSTEPS,
-                          gcols, grows, chunk_shift))
+                          gcols, grows, chunk_shift, geni_row_bytes))
         return CPG_OK;
     std::vector<double> cf;
     if (!pack_register_coefficients(coef, cf)) return CPG_OK;
@@ -2776,6 +2784,25 @@ int cpg_hip_get_stream(cpg_handle_t h, void **stream) {
     if (!h || !stream) { set_error("null argument"); return CPG_E_BADARG; }
     *stream = (void *)h->stream;
     return CPG_OK;
+}
+
+int cpg_hip_get_instance_tables(cpg_handle_t h, uint16_t *cols, int32_t n_cols, uint16_t *rows, int32_t n_rows, int32_t *row_bytes) {
+    if (!h || !cols || !rows || !row_bytes) { set_error("null argument"); return CPG_E_BADARG; }
+#ifdef CPG_GENI_HEADER
+    const int32_t nc = ((CPG_GENI_NSTEPS + 3) / 4) * 256, nr = ((CPG_GENI_NCHUNKS + 3) / 4) * 256;
+    if (h->conic || !h->R.gi_ok || !h->R.gi_cols || !h->R.gi_rows) { set_error("cpg_hip_get_instance_tables: the handle does not run the generated instance executor"); return CPG_E_BADARG; }
+    if (n_cols != nc || n_rows != nr) { set_error("cpg_hip_get_instance_tables: table sizes differ from the library's"); return CPG_E_BADARG; }
+    int rc = rt_set_device(h->device);
+    if (rc) return rc;
+    if ((rc = rt_d2h(h, cols, h->R.gi_cols, (size_t)nc * sizeof(uint16_t)))) return rc;
+    if ((rc = rt_d2h(h, rows, h->R.gi_rows, (size_t)nr * sizeof(uint16_t)))) return rc;
+    *row_bytes = geni_row_bytes ? 1 : 0;
+    return rt_sync(h);
+#else
+    (void)n_cols; (void)n_rows;
+    set_error("cpg_hip_get_instance_tables: this library has no generated instance executor");
+    return CPG_E_UNSUPPORTED;
+#endif
 }
 
 int cpg_hip_last_kernel_ms(cpg_handle_t h, float *ms) {

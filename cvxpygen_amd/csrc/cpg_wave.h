@@ -77,6 +77,33 @@ CPG_DEV double seg_sum_first_lit(double v, unsigned long long m0, unsigned long 
     if (S >= 3) v += lane_select(m2, row_shl<4>(v));
     return v;
 }
+// One stage of the same with move and select as ONE instruction per register half: v_cndmask_b32_dpp delivers the DPP-moved
+// source (0 where lane + N leaves the row) on the lanes whose VCC bit is clear and its second operand, a zero, on the others;
+// VCC takes the complement of the stage mask {LO, HI} as two literals.  The value is lane_select(mask, row_shl<N>(v)) bit for
+// bit.  The two scalar moves are also the two wait states a DPP read needs behind the vector instruction that wrote its
+// source -- hazards inside inline assembly are not the compiler's to see.  Anything but the device pass (the host pass, the
+// lock-step emulator) takes the two-step form.
+template <int N, unsigned LO, unsigned HI>
+CPG_DEV double sel_row_shl(double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    int rl, rh;
+    asm("s_mov_b32 vcc_lo, %4\n\ts_mov_b32 vcc_hi, %5\n\t"
+        "v_cndmask_b32_dpp %0, %2, %6, vcc row_shl:%7 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_cndmask_b32_dpp %1, %3, %6, vcc row_shl:%7 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "=&v"(rl), "=&v"(rh) : "v"(lo), "v"(hi), "i"(~LO), "i"(~HI), "v"(0), "i"(N) : "vcc");
+    return __hiloint2double(rh, rl);
+#else
+    return lane_select(((unsigned long long)HI << 32) | LO, row_shl<N>(v));
+#endif
+}
+template <int S, unsigned L0, unsigned H0, unsigned L1, unsigned H1, unsigned L2, unsigned H2>
+CPG_DEV double seg_sum_first_sel(double v) {
+    if (S >= 1) v += sel_row_shl<1, L0, H0>(v);
+    if (S >= 2) v += sel_row_shl<2, L1, H1>(v);
+    if (S >= 3) v += sel_row_shl<4, L2, H2>(v);
+    return v;
+}
 CPG_DEV double seg_sum_first_dyn(double v, unsigned mask, int stages) {   // stages wave-uniform
     switch (stages) {
         case 0: return v;

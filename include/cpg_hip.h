@@ -361,6 +361,13 @@ int cpg_hip_set_shared_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, 
 int cpg_hip_set_instance_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg, const double *coef, int32_t n_coef,
                                    const int8_t *row_class, double rho, double sigma);
 
+/* The generated instance executor's block-shared tables as the handle holds them on the device (behind
+ * cpg_hip_set_refactor* on a library with a generated instance executor): cols [n_cols = 256 * ceil(steps / 4)] the operand
+ * byte offsets [step / 4][lane][4], rows [n_rows = 256 * ceil(chunks / 4)] the output slots [chunk / 4][lane][4];
+ * *row_bytes = 1 when the slot table holds byte offsets (8 x slot; a header with CPG_GENI_LEAN), 0 when it holds slot numbers with
+ * the segment masks above bit 13.  For tests of the table layout. */
+int cpg_hip_get_instance_tables(cpg_handle_t h, uint16_t *cols, int32_t n_cols, uint16_t *rows, int32_t n_rows, int32_t *row_bytes);
+
 /* cpg_hip_set_refactor(h, rf), and -- when this library carries the generated resident executor of exactly this
  * family (cvxpygen_amd.codegen.resident_header; the merged program's fingerprint decides) -- the resident kernel's
  * tables: solves then run cpg_osqp_resident.h instead of the streaming kernel.  cpg_hip_get_setting(h,

@@ -58,7 +58,12 @@ def stats(lines, a, b):
     c = lambda p: sum(1 for l in seg if l.startswith(p))
     return dict(n=b - a + 1, fma=c('v_fma_f64') + c('v_fmac_f64'), mul=c('v_mul_f64'), ds_read=c('ds_read'),
                 ds_write=c('ds_write'), scratch_load=c('scratch_load'), scratch_store=c('scratch_store'),
-                global_load=c('global_load'), dpp=c('v_mov_b32_dpp'))
+                global_load=c('global_load'), dpp=c('v_mov_b32_dpp') + c('v_cndmask_b32_dpp'),
+                # what surrounds the arithmetic: field extraction (v_and_b32, v_lshrrev_b32, v_bfe_u32), selects, waits; `code`
+                # counts instructions only (n also counts the labels and comments of the listing)
+                extract=c('v_and_b32') + c('v_lshrrev_b32') + c('v_bfe_u32'), cndmask=c('v_cndmask_b32') - c('v_cndmask_b32_dpp'),
+                waitcnt=c('s_waitcnt'), nop=c('s_nop'),
+                code=sum(1 for l in seg if l and not l.startswith((';', '.'))))
 
 
 def address_reloads(lines):
