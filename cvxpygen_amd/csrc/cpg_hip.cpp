@@ -579,7 +579,7 @@ static size_t instance_kernel_lds(const cpg_solver_s *h) {
     const size_t nq = (size_t)(h->F.n + h->F.m);
     size_t per_wave = (size_t)(CPG_GENI_NSLOTS + CPG_GEN_EXTRA_SLOTS) + nq + (nq & 1);
 #ifdef CPG_GENI_FAC_NSTEPS
-    const size_t fac = (size_t)CPG_GENI_FAC_ZERO + 1;
+    const size_t fac = (size_t)CPG_GENI_FAC_ZERO + 1 + CPG_GENI_FAC_DUMMY_DOUBLES;
 #else
     const size_t fac = (size_t)h->R.nnzL + nq;
 #endif
@@ -1764,7 +1764,9 @@ static int set_instance_executor(cpg_handle_t h, const cpg_osqp_refactor_t *r, c
         const size_t one = nd + nx;                               // (merged programs)
         unsigned hsh2 = 0x811C9DC5u;
         auto mix = [&](unsigned v) { for (int k = 0; k < 4; k++) { hsh2 = (hsh2 ^ ((v >> (8 * k)) & 0xFFu)) * 0x01000193u; } };
-        ok = g.fac_chunks == CPG_GENI_FAC_NCHUNKS && fac_end - 1 == (size_t)CPG_GENI_FAC_ZERO && fac_end <= 0xFFFFu;
+        // (by-level form: idle lanes carry the dummy position behind the 0.0 as their destination, no 0xFFFF to test for)
+        const unsigned idle_dst = CPG_GENI_FAC_DUMMY_DOUBLES ? (unsigned)fac_end : 0xFFFFu;
+        ok = g.fac_chunks == CPG_GENI_FAC_NCHUNKS && fac_end - 1 == (size_t)CPG_GENI_FAC_ZERO && fac_end + CPG_GENI_FAC_DUMMY_DOUBLES <= 0xFFFFu;
 #ifdef CPG_GENI_FAC_ONE
         ok = ok && one == (size_t)CPG_GENI_FAC_ONE;
 #endif
@@ -1774,7 +1776,7 @@ static int set_instance_executor(cpg_handle_t h, const cpg_osqp_refactor_t *r, c
         if (ok) {
             const unsigned long long Z = (unsigned long long)(fac_end - 1);
             gtri.assign((size_t)CPG_GENI_FAC_NSTEPS * 64, Z | (Z << 16) | (Z << 32));
-            gdk.assign((size_t)g.fac_chunks * 64, 0xFFFFu);
+            gdk.assign((size_t)g.fac_chunks * 64, idle_dst);
             gkc.assign((size_t)g.fac_chunks * 64, 0.0);
             size_t step = 0;
             for (int c = 0; ok && c < g.fac_chunks; c++) {

@@ -22,6 +22,21 @@
 // registers (cvxpygen_amd/codegen.py::emit_instance_program)
 #include CPG_GENI_HEADER
 #endif
+// the by-level form of the generated factorisation (codegen._emit_factor_levels) has no branch around a chunk's store: idle
+// lanes store to a dummy position behind the 0.0 of the factor slice (two doubles: the slice stays even) -- the slice's
+// length here, in cpg_hip.cpp (instance_kernel_lds) and in codegen.instance_program_fits change together
+#ifdef CPG_GENI_FAC_BY_LEVEL
+#define CPG_GENI_FAC_DUMMY_DOUBLES 2u
+#else
+#define CPG_GENI_FAC_DUMMY_DOUBLES 0u
+#endif
+// comment-only markers in the compiled listing (scripts/isa_hot_loops.py delimits the factorisation and the coefficient
+// extraction of the instance kernel by them); nothing in a host build
+#if defined(__HIP_DEVICE_COMPILE__)
+#define CPG_REGION_MARK(s) asm volatile("; cpg-region " s)
+#else
+#define CPG_REGION_MARK(s) ((void)0)
+#endif
 #ifdef CPG_GENS_HEADER
 // straight-line executor of the family's per-instance substitution program on per-instance matrices: coefficients and tables
 // from global memory at static addresses (cvxpygen_amd/codegen.py::stream_header)
@@ -587,7 +602,8 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
     size_t per_wave = (size_t)ldw + (GENI ? (size_t)(N + (N & 1u)) : 0u);
 #ifdef CPG_GENI_FAC_NSTEPS
     // (+ the zero slot idle lanes of the generated factorisation read; a merged program: [M | 1/d | X | 1.0 | 0.0], see below)
-    const size_t fac_doubles = (size_t)CPG_GENI_FAC_ZERO + 1u;
+    // (by-level form: + the dummy doubles idle lanes store to)
+    const size_t fac_doubles = (size_t)CPG_GENI_FAC_ZERO + 1u + CPG_GENI_FAC_DUMMY_DOUBLES;
 #else
     const size_t fac_doubles = (size_t)R.nnzL + N;
 #endif
@@ -640,10 +656,15 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
 
         // (experiments, generated instance kernel only, debug_stage 20: 100 MHz time stamps of the instance's stages replace
         // its first primal results -- scripts/gpu_probe_instance.py)
-        const bool probe = GENI && __builtin_expect(S.debug_stage == 20, 0);
+        // (debug_stage 24: two more stamps inside the factorisation stage -- factorised, coefficients in registers -- in front
+        // of the stage's own, which then closes the slice restore)
+        // (the mode is tested where the two stamps are taken: a second flag kept across the instance loop shifted the kernel's
+        // register allocation)
+        const bool probe = GENI && __builtin_expect(S.debug_stage == 20 || S.debug_stage == 24, 0);
         unsigned long long ts[8];
         int n_ts = 0;
 #define CPG_INST_PROBE() do { if (GENI && probe && n_ts < 8) ts[n_ts++] = cpgw::clock100(); } while (0)
+#define CPG_INST_PROBE_SPLIT() do { if (GENI && probe && S.debug_stage == 24 && n_ts < 8) ts[n_ts++] = cpgw::clock100(); } while (0)
         CPG_INST_PROBE();
 #ifdef CPG_GENI_HEADER
         // generated instance kernel: an instance that starts at the family's rho and sigma needs no factorisation of its own when
@@ -827,12 +848,18 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
             if (lane == 0) w[CPG_GENI_FAC_ONE] = 1.0;
 #endif
             cpgw::lds_order();
+            CPG_REGION_MARK("factor begin");
             numeric_ldl_gen(R.gf_tri, R.gf_dk, R.gf_kc, (const double *)B.rinv, w, lane);
+            CPG_REGION_MARK("factor end");
 #else
             numeric_ldl_m<true>(R, w, w + R.nnzL, (const double *)B.rinv, lane);
 #endif
+            CPG_INST_PROBE_SPLIT();      // (debug_stage 24: factorised)
+            CPG_REGION_MARK("coefficients begin");
             load_instance_coefficients(R, w, w + R.nnzL, cf, lane);
+            CPG_REGION_MARK("coefficients end");
             cpgw::lds_order();
+            CPG_INST_PROBE_SPLIT();      // (coefficients in registers; the stage's own stamp follows the slice restore)
             // the slice goes back to its ADMM use: idle lanes of a step gather the zero slot, idle lanes of a chunk
             // store to the dummy slots behind the program's own (everything starts finite); q and u of the instance
             for (unsigned t = (unsigned)lane; t < (unsigned)ldw; t += 64u) w[t] = 0.0;

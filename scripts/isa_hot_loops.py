@@ -6,6 +6,9 @@ gfx950 to assembly with the family's definitions and reports, per kernel,
   * scratch accesses INSIDE the ADMM loop of the generated instance kernel (must be 0: the wavefronts' scratch does not
     fit the L2, every reload there is a memory-latency stall in a loop that is a chain of latencies already) and, for
     the streaming kernels, inside the stream loop and in the rest of an iteration,
+  * the factorisation and coefficient-extraction regions of the generated instance kernel (delimited by comment-only
+    markers, at the set-up site and at the in-loop site): instructions, ds_read, full LDS drains (lgkmcnt(0)), vmcnt
+    waits, conditional branches, scratch accesses -- next to the number of schedule levels that have a step,
   * "address-reload sequences": a 64-bit address reloaded from scratch right in front of the global access that uses it
     -- the signature of instance-invariant addresses computed outside the persistent instance loop (HISTORY.md 4.5).
 
@@ -78,6 +81,44 @@ def address_reloads(lines):
     return hits, sum(1 for l in code if l.startswith('scratch_load')), len(code)
 
 
+def regions(lines):
+    """(name, first line, last line) of the stretches of a kernel's listing between the comment-only markers
+    `; cpg-region <name> begin` / `end` (CPG_REGION_MARK in csrc/cpg_osqp_refactor.h: the generated factorisation and the
+    coefficient extraction of the instance kernel; each is inlined at the set-up site and at the in-loop site)"""
+    out, open_ = [], {}
+    for i, l in enumerate(lines):
+        mm = re.search(r'; cpg-region (\w+) (begin|end)', l)
+        if not mm:
+            continue
+        if mm.group(2) == 'begin':
+            open_[mm.group(1)] = i
+        elif mm.group(1) in open_:
+            out.append((mm.group(1), open_.pop(mm.group(1)), i))
+    return out
+
+
+def region_stats(lines, a, b):
+    seg = [l.strip() for l in lines[a:b + 1]]
+    code = [l for l in seg if l and not l.startswith((';', '.'))]
+    c = lambda p: sum(1 for l in code if l.startswith(p))
+    waits = [l for l in code if l.startswith('s_waitcnt')]
+    return dict(instructions=len(code), ds_read=c('ds_read'), ds_write=c('ds_write'), global_load=c('global_load'),
+                lgkmcnt0=sum(1 for l in waits if 'lgkmcnt(0)' in l), vmcnt=sum(1 for l in waits if 'vmcnt' in l),
+                cond_branch=c('s_cbranch_'), scratch=c('scratch_'), div_chain=c('v_div_fmas_f64'))
+
+
+def factor_level_counts(plan):
+    """levels of the instance kernel's factorisation schedule, and those of them with at least one step"""
+    from cvxpygen_amd import refactor_plan
+    d = plan.desc
+    o = plan.osqp_shared or plan.osqp
+    Ps, As = o.pruned(d.P, d.A)
+    rpl = refactor_plan.shared_mode_plan(Ps, As, o)
+    ct = rpl.merged.f_ctab if rpl.merged is not None else rpl.fac.ctab
+    lv = codegen.factor_levels(ct)
+    return len(lv), sum(1 for l in lv if any(int(ct[c][0]) for c in l))
+
+
 def main():
     fam = sys.argv[1] if len(sys.argv) > 1 else 'mpc12'
     keep = sys.argv[sys.argv.index('--keep') + 1] if '--keep' in sys.argv else None
@@ -109,6 +150,12 @@ def main():
                 seen = True
                 print('    ADMM loop:', st)
                 ok &= st['scratch_load'] == 0 and st['scratch_store'] == 0
+            regs = regions(lines)
+            if regs:
+                n_lv, n_lv_steps = factor_level_counts(plan)
+                print(f'    factorisation schedule: {n_lv} levels, {n_lv_steps} with a step')
+                for nm, a, b in regs:
+                    print(f'    region {nm:<12} lines {a:>6} - {b:>6}: {region_stats(lines, a, b)}')
         elif 'osqp_refactor' in name:
             stream = [(a, b) for a, b in lps if 1000 < b - a < 2600 and stats(lines, a, b)['fma'] >= 8
                       and stats(lines, a, b)['global_load'] in (4, 8)]
