@@ -63,6 +63,7 @@ struct cpg_solver_s {
     cpg::DevRefactor R{};
     bool refactor_mode = false;
     std::vector<void *> refactor_owned;
+    int coef_scale_entries = 0;          // entries of R.gi_scale in front of its idle padding (two-pass coefficient extraction)
     cpg::DevResident Rs{};               // resident per-instance factor kernel (cpg_hip_set_resident); Rs.ok: in use
     std::vector<void *> resident_owned;
     cpg::DevGradient Gd{};
@@ -1699,8 +1700,8 @@ static int set_instance_executor(cpg_handle_t h, const cpg_osqp_refactor_t *r, c
     const size_t n = h->F.n, m = h->F.m, N = n + m;
     int rc = CPG_OK;
     R.gi_ok = 0;
-    std::vector<unsigned short> gcols, grows, glcol;
-    std::vector<unsigned> gsrc, gdk;
+    std::vector<unsigned short> gcols, grows, glcol, goff;
+    std::vector<unsigned> gsrc, gdk, gscale;
     std::vector<unsigned long long> gtri;
     std::vector<double> gkc;
 #ifdef CPG_GENI_N
@@ -1755,6 +1756,32 @@ static int set_instance_executor(cpg_handle_t h, const cpg_osqp_refactor_t *r, c
             }
         }
     }
+#ifdef CPG_COEF_TWO_PASS_ACTIVE
+    if (ok) {
+        // two-pass extraction (gather_instance_coefficients) on the slice [M | 1/d | X | 1.0 | 0.0 | dummy]: the M entries behind
+        // kind-2 coefficients, each ONCE and in ascending order, with the position of their column's reciprocal pivot; and per
+        // (register, lane) the byte offset of its source once those are scaled in place
+        const size_t zero = (size_t)CPG_GENI_FAC_ZERO, one = (size_t)CPG_GENI_FAC_ONE, dummy = zero + 1;
+        ok = CPG_GENI_FAC_DUMMY_DOUBLES >= 1u && nd + nx == one && one + 1 == zero && 8 * (zero + 1 + CPG_GENI_FAC_DUMMY_DOUBLES) <= 0xFFFFu;
+        std::vector<char> scaled(ok ? (size_t)r->nnzL : 0, 0);
+        goff.assign((size_t)CPG_GENI_NREGS * 64, (unsigned short)(8 * zero));
+        for (size_t at = 0; ok && at < gsrc.size(); at++) {
+            const unsigned kind = gsrc[at] >> 28, idx = gsrc[at] & 0x0FFFFFFFu;
+            size_t pos = zero;                                    // (kind 0, and lanes no step takes)
+            if (kind == 1) pos = one;
+            else if (kind == 2) { pos = idx; scaled[idx] = 1; }   // (idx < nnzL: checked above)
+            else if (kind == 3) { pos = (size_t)r->nnzL + idx; if (idx >= N + nx) ok = false; }
+            goff[at] = (unsigned short)(8 * pos);
+        }
+        for (size_t e = 0; ok && e < scaled.size(); e++)
+            if (scaled[e]) gscale.push_back((unsigned)e | (((unsigned)r->nnzL + (unsigned)r->Lcol[e]) << 16));
+        for (size_t k = 0; ok && k < gscale.size(); k++) if ((gscale[k] >> 16) >= nd) ok = false;     // (a pivot position)
+        ok = ok && (gscale.size() + 63) / 64 == (size_t)CPG_GENI_COEF_SCALE_ROUNDS;
+        h->coef_scale_entries = ok ? (int)gscale.size() : 0;
+        // (a program without an L entry has no round; its table is one round of idle words, never read)
+        if (ok) gscale.resize((size_t)(CPG_GENI_COEF_SCALE_ROUNDS > 0 ? CPG_GENI_COEF_SCALE_ROUNDS : 1) * 64, (unsigned)dummy | ((unsigned)zero << 16));
+    }
+#endif
 #ifdef CPG_GENI_FAC_NSTEPS
     if (ok) {
         // tables of the generated factorisation: its header fixes (steps, level end, group width) per chunk and the term
@@ -1828,6 +1855,10 @@ static int set_instance_executor(cpg_handle_t h, const cpg_osqp_refactor_t *r, c
         if ((rc = upload<unsigned short>(h, own, gcols.data(), gcols.size(), &R.gi_cols))) return rc;
         if ((rc = upload<unsigned short>(h, own, grows.data(), grows.size(), &R.gi_rows))) return rc;
         if ((rc = upload<unsigned>(h, own, gsrc.data(), gsrc.size(), &R.gi_src))) return rc;
+#ifdef CPG_COEF_TWO_PASS_ACTIVE
+        if ((rc = upload<unsigned>(h, own, gscale.data(), gscale.size(), &R.gi_scale))) return rc;
+        if ((rc = upload<unsigned short>(h, own, goff.data(), goff.size(), &R.gi_off))) return rc;
+#endif
     }
     if ((rc = rt_sync(h))) return rc;                             // (the host vectors above end here)
     R.gi_ok = ok ? 1 : 0;
@@ -1928,7 +1959,7 @@ int cpg_hip_set_refactor(cpg_handle_t h, const cpg_osqp_refactor_t *r) {
         if ((rc = upload<double>(h, own, einv.data(), m, &R.Einvs))) return rc;
     }
     R.gf_tri = nullptr; R.gf_dk = nullptr; R.gf_kc = nullptr;
-    R.gi_ok = 0; R.gi_cols = R.gi_rows = nullptr; R.gi_src = nullptr; R.gi_lcol = nullptr; R.fac_kc = nullptr; R.fac_krow = nullptr; R.fac_kc_cl = nullptr; R.fac_krow_cl = nullptr; R.fac_kind_cl = nullptr; R.fac_idx_cl = nullptr;
+    R.gi_ok = 0; R.gi_cols = R.gi_rows = nullptr; R.gi_src = nullptr; R.gi_lcol = nullptr; R.gi_scale = nullptr; R.gi_off = nullptr; R.fac_kc = nullptr; R.fac_krow = nullptr; R.fac_kc_cl = nullptr; R.fac_krow_cl = nullptr; R.fac_kind_cl = nullptr; R.fac_idx_cl = nullptr;
     std::vector<double> fkc, fkc_cl;                              // alive until the sync below
     std::vector<int> fkrow, fkrow_cl;
 
@@ -2803,6 +2834,25 @@ int cpg_hip_get_instance_tables(cpg_handle_t h, uint16_t *cols, int32_t n_cols, 
 #else
     (void)n_cols; (void)n_rows;
     set_error("cpg_hip_get_instance_tables: this library has no generated instance executor");
+    return CPG_E_UNSUPPORTED;
+#endif
+}
+
+int cpg_hip_get_coefficient_tables(cpg_handle_t h, uint32_t *scale, int32_t n_scale, uint16_t *offsets, int32_t n_offsets, int32_t *n_entries) {
+    if (!h || !scale || !offsets || !n_entries) { set_error("null argument"); return CPG_E_BADARG; }
+#ifdef CPG_COEF_TWO_PASS_ACTIVE
+    const int32_t ns = (CPG_GENI_COEF_SCALE_ROUNDS > 0 ? CPG_GENI_COEF_SCALE_ROUNDS : 1) * 64, no = CPG_GENI_NREGS * 64;
+    if (h->conic || !h->R.gi_ok || !h->R.gi_scale || !h->R.gi_off) { set_error("cpg_hip_get_coefficient_tables: the handle does not run the generated instance executor"); return CPG_E_BADARG; }
+    if (n_scale != ns || n_offsets != no) { set_error("cpg_hip_get_coefficient_tables: table sizes differ from the library's"); return CPG_E_BADARG; }
+    int rc = rt_set_device(h->device);
+    if (rc) return rc;
+    if ((rc = rt_d2h(h, scale, h->R.gi_scale, (size_t)ns * sizeof(uint32_t)))) return rc;
+    if ((rc = rt_d2h(h, offsets, h->R.gi_off, (size_t)no * sizeof(uint16_t)))) return rc;
+    *n_entries = h->coef_scale_entries;
+    return rt_sync(h);
+#else
+    (void)n_scale; (void)n_offsets;
+    set_error("cpg_hip_get_coefficient_tables: this library extracts the instance coefficients register by register");
     return CPG_E_UNSUPPORTED;
 #endif
 }

@@ -106,6 +106,12 @@ struct DevRefactor {
     const unsigned short *gi_cols, *gi_rows;
     const unsigned *gi_src;
     const unsigned short *gi_lcol;      // [step][lane] column of the L entry behind a kind-2 coefficient
+    // two-pass coefficient extraction (CPG_GENI_COEF_TWO_PASS, gather_instance_coefficients): gi_scale [round][lane] = position
+    // of an M entry that a kind-2 coefficient reads | position of its column's reciprocal pivot << 16, every such entry once
+    // (idle lanes of the last round: the dummy double | the 0.0 << 16); gi_off [register][lane] = byte offset in the factor
+    // slice of what gi_src names once those entries are scaled (kind 0 and untaken lanes: the 0.0, kind 1: the 1.0)
+    const unsigned *gi_scale;
+    const unsigned short *gi_off;
     // generated factorisation of shared-matrix mode (numeric_ldl_gen of the family's cpg_instance_<name>.h): operand positions
     // a | b << 16 | k << 32 per (step, lane), destination | (rho row + 1) << 16 per (chunk, lane); see codegen.emit_factor_program
     const unsigned long long *gf_tri;
@@ -493,6 +499,65 @@ CPG_DEV void load_instance_coefficients(const DevRefactor &R, const double *Ml, 
     }
 }
 
+#if defined(CPG_GENI_COEF_TWO_PASS) && defined(CPG_GENI_FAC_BY_LEVEL) && defined(CPG_GENI_FAC_ONE)
+// The same registers in two passes over the merged factor slice w = [M | 1/d | X | 1.0 | 0.0 | dummy] (headers with the
+// by-level generated factorisation; codegen.COEFFICIENT_TWO_PASS).  Only a kind-2 coefficient needs arithmetic, nothing
+// reads M between the factorisation and the slice restore, and the restore zeroes the slice: so
+//   1. every M entry behind a kind-2 coefficient is scaled IN PLACE, M[e] = -(M[e] * Dinv[col_e]) -- the product and the
+//      negation of load_instance_coefficients, the same bits --, lane l of round r taking entry 64 r + l of the host's list
+//      (gi_scale: each entry once, however many (register, lane) pairs read it; idle lanes of the last round scale the dummy
+//      double behind the 0.0, nothing is tested).  The coefficient registers are dead here -- every one is about to be
+//      overwritten --, so the gathers of CPG_COEF_SCALE_BATCH rounds are in flight together, next to
+//      the words of the batch behind them;
+//   2. a coefficient is ONE ds_read at the byte offset the host computed for its (register, lane) (gi_off): the scaled M
+//      entry, the entry of [1/d | X], the 1.0 or the 0.0.  No kind, no select, no second operand; the offset word of a
+//      register (one VGPR) dies where its coefficient (two) is born.
+// (opaque lane: see load_instance_coefficients)
+#define CPG_COEF_TWO_PASS_ACTIVE 1
+#ifndef CPG_COEF_SCALE_BATCH
+#define CPG_COEF_SCALE_BATCH CPG_GENI_COEF_SCALE_ROUNDS      // rounds of pass 1 in flight together (profiles/coefficient_gather_resources.txt)
+#endif
+#ifndef CPG_COEF_OFFSET_BATCH
+#define CPG_COEF_OFFSET_BATCH CPG_GENI_NREGS                 // offset words of pass 2 requested together
+#endif
+CPG_DEV void gather_instance_coefficients(const DevRefactor &R, double *w, double (&cf)[CPG_GENI_NREGS], int lane) {
+    constexpr int NR = CPG_GENI_COEF_SCALE_ROUNDS, NB = CPG_COEF_SCALE_BATCH < NR ? CPG_COEF_SCALE_BATCH : NR;
+    const unsigned ln = (unsigned)cpgw::opaque(lane);
+    // (the words of a batch are requested one batch ahead, behind the gathers of the batch in front: all NR of them requested up
+    // front, one register each, moved the allocation of the whole kernel whatever the batch -- profiles/coefficient_gather_resources.txt)
+    constexpr int NA = NB > 0 ? NB : 1;        // (no round at all: a program without an L entry, everything in X)
+    unsigned sw[NA];
+#pragma unroll
+    for (int t = 0; t < NB; t++) sw[t] = cpgw::gld(R.gi_scale, (unsigned)t * 64u + ln);
+#pragma unroll
+    for (int r0 = 0; r0 < NR; r0 += NB) {
+        double a[NA], d[NA];
+        unsigned nx[NA];
+#pragma unroll
+        for (int t = 0; t < NB; t++) if (r0 + t < NR) { a[t] = w[sw[t] & 0xFFFFu]; d[t] = w[sw[t] >> 16]; }
+#pragma unroll
+        for (int t = 0; t < NB; t++) if (r0 + NB + t < NR) nx[t] = cpgw::gld(R.gi_scale, (unsigned)(r0 + NB + t) * 64u + ln);
+        cpgw::sched_fence();
+#pragma unroll
+        for (int t = 0; t < NB; t++) if (r0 + t < NR) w[sw[t] & 0xFFFFu] = -(a[t] * d[t]);
+        cpgw::sched_fence();
+#pragma unroll
+        for (int t = 0; t < NB; t++) if (r0 + NB + t < NR) sw[t] = nx[t];
+    }
+    cpgw::lds_order();
+    constexpr int OB = CPG_COEF_OFFSET_BATCH < CPG_GENI_NREGS ? CPG_COEF_OFFSET_BATCH : CPG_GENI_NREGS;
+#pragma unroll
+    for (int t0 = 0; t0 < CPG_GENI_NREGS; t0 += OB) {
+        unsigned short off[OB];
+#pragma unroll
+        for (int t = 0; t < OB; t++) if (t0 + t < CPG_GENI_NREGS) off[t] = cpgw::gld(R.gi_off, (unsigned)(t0 + t) * 64u + ln);
+#pragma unroll
+        for (int t = 0; t < OB; t++) if (t0 + t < CPG_GENI_NREGS) cf[t0 + t] = *(const double *)((const char *)w + off[t]);
+        if (OB < CPG_GENI_NREGS) cpgw::sched_fence();
+    }
+}
+#endif
+
 #ifdef CPG_GENI_NNZX
 // the merged program as the shared kernel's executor (osqp_shared_body<.., SharedRegExec>): every instance there has the
 // family's matrix and rho, so its coefficients come from ONE host-side factorisation (cpg_hip_set_shared_registers) and
@@ -856,7 +921,11 @@ CPG_DEV void osqp_refactor_body(const DevFamily &F0, const DevRefactor &R, const
 #endif
             CPG_INST_PROBE_SPLIT();      // (debug_stage 24: factorised)
             CPG_REGION_MARK("coefficients begin");
+#ifdef CPG_COEF_TWO_PASS_ACTIVE
+            gather_instance_coefficients(R, w, cf, lane);
+#else
             load_instance_coefficients(R, w, w + R.nnzL, cf, lane);
+#endif
             CPG_REGION_MARK("coefficients end");
             cpgw::lds_order();
             CPG_INST_PROBE_SPLIT();      // (coefficients in registers; the stage's own stamp follows the slice restore)

@@ -136,7 +136,7 @@ class CpgLibrary:
 
     SYMBOLS = ['cpg_hip_device_count', 'cpg_hip_create_osqp', 'cpg_hip_create_clarabel', 'cpg_hip_destroy', 'cpg_hip_last_error',
                'cpg_hip_status_string', 'cpg_hip_set_default_settings', 'cpg_hip_set_setting',
-               'cpg_hip_get_setting', 'cpg_hip_set_build_option', 'cpg_hip_set_handover', 'cpg_hip_last_phase_ms', 'cpg_hip_set_update', 'cpg_hip_set_refactor', 'cpg_hip_set_refactor_merged', 'cpg_hip_set_shared_registers', 'cpg_hip_set_instance_registers', 'cpg_hip_get_instance_tables', 'cpg_hip_set_resident', 'cpg_hip_set_gradient', 'cpg_hip_gradient_batch',
+               'cpg_hip_get_setting', 'cpg_hip_set_build_option', 'cpg_hip_set_handover', 'cpg_hip_last_phase_ms', 'cpg_hip_set_update', 'cpg_hip_set_refactor', 'cpg_hip_set_refactor_merged', 'cpg_hip_set_shared_registers', 'cpg_hip_set_instance_registers', 'cpg_hip_get_instance_tables', 'cpg_hip_get_coefficient_tables', 'cpg_hip_set_resident', 'cpg_hip_set_gradient', 'cpg_hip_gradient_batch',
                'cpg_hip_set_gradient_vars', 'cpg_hip_gradient_batch_device',
                'cpg_hip_solve_batch',
                'cpg_hip_solve_batch_device', 'cpg_hip_solve_batch_state', 'cpg_hip_solve_batch_device_state', 'cpg_hip_solve_batches_pipelined', 'cpg_hip_host_malloc',
@@ -170,6 +170,7 @@ class CpgLibrary:
         L.cpg_hip_set_resident.argtypes = [C.c_void_p, C.POINTER(_Refactor), C.POINTER(_Resident)]
         L.cpg_hip_set_refactor_merged.argtypes = [C.c_void_p, C.POINTER(_Refactor), C.POINTER(_Resident)]
         L.cpg_hip_get_instance_tables.argtypes = [C.c_void_p, _u16p, C.c_int32, _u16p, C.c_int32, C.POINTER(C.c_int32)]
+        L.cpg_hip_get_coefficient_tables.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32, _u16p, C.c_int32, C.POINTER(C.c_int32)]
         L.cpg_hip_set_shared_registers.argtypes = [C.c_void_p, C.POINTER(_Resident), _dp, C.c_int32, C.c_double, C.c_double]
         L.cpg_hip_set_instance_registers.argtypes = [C.c_void_p, C.POINTER(_Resident), _dp, C.c_int32, _i8p, C.c_double, C.c_double]
         L.cpg_hip_set_gradient.argtypes = [C.c_void_p, C.POINTER(_Gradient)]

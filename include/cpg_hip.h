@@ -368,6 +368,13 @@ int cpg_hip_set_instance_registers(cpg_handle_t h, const cpg_osqp_resident_t *mg
  * the segment masks above bit 13.  For tests of the table layout. */
 int cpg_hip_get_instance_tables(cpg_handle_t h, uint16_t *cols, int32_t n_cols, uint16_t *rows, int32_t n_rows, int32_t *row_bytes);
 
+/* The two tables of the instance kernel's two-pass coefficient extraction as the handle holds them on the device (a library
+ * whose instance header defines CPG_GENI_COEF_TWO_PASS; any other returns CPG_E_UNSUPPORTED): scale [n_scale = 64 *
+ * max(CPG_GENI_COEF_SCALE_ROUNDS, 1)] = position of an L entry a coefficient reads | position of its column's reciprocal pivot << 16, in the
+ * factor slice [M | 1/d | X | 1.0 | 0.0 | dummy], *n_entries of them followed by the words of idle lanes; offsets [n_offsets =
+ * 64 * CPG_GENI_NREGS] = byte offset in that slice of the coefficient of every (register, lane).  For tests of the tables. */
+int cpg_hip_get_coefficient_tables(cpg_handle_t h, uint32_t *scale, int32_t n_scale, uint16_t *offsets, int32_t n_offsets, int32_t *n_entries);
+
 /* cpg_hip_set_refactor(h, rf), and -- when this library carries the generated resident executor of exactly this
  * family (cvxpygen_amd.codegen.resident_header; the merged program's fingerprint decides) -- the resident kernel's
  * tables: solves then run cpg_osqp_resident.h instead of the streaming kernel.  cpg_hip_get_setting(h,
